@@ -6,7 +6,7 @@ streams of tests/golden/bench_aim (SURVEY.md §8(d) recipe: QP {22,27,32,37},
 seeded crops / flips of the fixture content + noise, 110-220 KB per picture)
 tiled x16; every frame is decoded independently (no dedupe).  The lighter
 16-stream set of rounds 1-5 (tests/golden/bench, 72 KB per picture) is
-reported beside it as value_light.
+reported beside it as value_light (with --full).
 
 One step = one full transcode of the batch: host entropy threads
 (CABAC -> job records), H2D, the HIP pixel pipeline (K1 recon, K2 deblock,
@@ -18,6 +18,12 @@ Multi-GPU (`torch.distributed.run --nproc-per-node N`): one process per GPU,
 each transcodes its own 1024-frame batch (weak scaling, no data-path
 collective); a barrier brackets the timed region and rank 0 reports the max
 time over ranks.  The only collectives are the counter reductions at the end.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line.  `--dump-outputs DIR` also writes what the last timed step returned
+(dump_outputs).  Everything else the benchmark measures or checks -- the md5 check of the
+JPEGs against tests/golden/bench_manifest.json, the configs[0] single-call latencies,
+value_light / value_aim and the host-thread sweep, the CPU baseline -- runs only with `--full`.
 """
 import argparse
 import ctypes
@@ -27,6 +33,7 @@ import resource
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "h264-h265-to-jpeg_amd"))
@@ -164,6 +171,41 @@ def verify_outputs(batch, out, offs, lens, manifest):
         if hashlib.md5(mv[offs[i]:offs[i] + lens[i]]).hexdigest() != ent["jpeg_md5"]:
             bad += 1
     return len(batch), bad, missing
+
+
+DUMP_SEED = 20240611
+DUMP_SAMPLE_BYTES = 12 << 20  # JPEG bytes kept as float32: 48 MiB of the 64 MB a dump may take
+
+
+def dump_outputs(path, out, offs, lens, status, n, suffix=""):
+    """--dump-outputs: what a caller of the timed path received from the last timed step, as
+    float64 / float32 .npy files, so that two builds can be compared output for output.
+    For all n pictures: jpeg_status (0 = ok), jpeg_lens (bytes) and jpeg_crc32 (zlib.crc32 of the
+    JPEG, exact in float64).  The JPEG bytes themselves for a fixed seeded sample of pictures that
+    fits DUMP_SAMPLE_BYTES: jpeg_sample_index (picture numbers, ascending) and jpeg_sample_bytes
+    (their JPEGs back to back, lengths in jpeg_lens)."""
+    import random
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    raw = np.frombuffer(out, dtype=np.uint8)
+    ok = [status[i] == 0 for i in range(n)]
+    ln = [int(lens[i]) if ok[i] else 0 for i in range(n)]
+    of = [int(offs[i]) for i in range(n)]
+    crc = [zlib.crc32(raw[of[i]:of[i] + ln[i]]) if ok[i] else 0 for i in range(n)]
+    picked, used = [], 0
+    for i in random.Random(DUMP_SEED).sample(range(n), n):
+        if ok[i] and used + ln[i] <= DUMP_SAMPLE_BYTES:
+            picked.append(i)
+            used += ln[i]
+    picked.sort()
+    sample = np.concatenate([raw[of[i]:of[i] + ln[i]] for i in picked]) if picked else np.zeros(0, np.uint8)
+    arrays = {"jpeg_status": np.array([status[i] for i in range(n)], dtype=np.float64),
+              "jpeg_lens": np.array(ln, dtype=np.float64),
+              "jpeg_crc32": np.array(crc, dtype=np.float64),
+              "jpeg_sample_index": np.array(picked, dtype=np.float64),
+              "jpeg_sample_bytes": sample.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def shard_lpt(costs, world):
@@ -330,6 +372,13 @@ def main():
     ap.add_argument("--workload", default="hevc1080", choices=sorted(WORKLOADS),
                     help="hevc1080 = the BASELINE metric's config; the others are configs[2]/[3]/[4]")
     ap.add_argument("--streams", default=None, help="override the workload's stream glob")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the md5 check of "
+                         "the last step's JPEGs against tests/golden/bench_manifest.json, the configs[0] "
+                         "single-call latencies, value_light / value_aim with the host-thread sweep, and the CPU "
+                         "baseline (each can be left out again with the --no-* switches below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync", action="store_true",
                     help="one synchronous h2j_engine_transcode per step (no cross-step overlap)")
@@ -338,6 +387,8 @@ def main():
     ap.add_argument("--no-aim", action="store_true",
                     help="skip value_aim (configs[1] on the 100-250 KB/picture set) and the host-thread sweep")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -439,13 +490,16 @@ def main():
     # host CPU time of this process (all threads) over the timed region, in busy cores
     host_cores = ((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)) / max(elapsed, 1e-9)
     elapsed, total_frames = reduce_over_ranks(dist, elapsed, n * args.steps, local)
-    # outside the timed region: every JPEG of the last timed step against the oracle's md5s
-    man_path = os.path.join(ROOT, "tests", "golden", "bench_manifest.json")
-    manifest = json.load(open(man_path)) if os.path.exists(man_path) else {}
-    out, offs, lens, _ = last_out[0]
-    checked, bad, missing = verify_outputs(batch, out, offs, lens, manifest)
-    bad_all = sum_over_ranks(dist, bad + missing, local)
-    checked_all = sum_over_ranks(dist, checked, local)
+    out, offs, lens, status = last_out[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, offs, lens, status, n, f".rank{rank}" if world > 1 else "")
+    if args.full:
+        # outside the timed region: every JPEG of the last timed step against the oracle's md5s
+        man_path = os.path.join(ROOT, "tests", "golden", "bench_manifest.json")
+        manifest = json.load(open(man_path)) if os.path.exists(man_path) else {}
+        checked, bad, missing = verify_outputs(batch, out, offs, lens, manifest)
+        bad_all = sum_over_ranks(dist, bad + missing, local)
+        checked_all = sum_over_ranks(dist, checked, local)
 
     if rank == 0:
         steps = args.steps
@@ -529,21 +583,22 @@ def main():
             "d2h_payload_GBps": round(per.get("payload_copied_bytes", 0.0) / max(per.get("d2h_payload_ms", 0.0), 1e-9) / 1e6, 2),
             "h2d_MB_per_step": round(per.get("h2d_bytes", 0.0) / 1e6, 2),
             "h2d_GBps": round(per.get("h2d_bytes", 0.0) / max(per.get("h2d_ms", 0.0), 1e-9) / 1e6, 2),
-            "outputs_verified": bool(manifest) and bad_all == 0,
-            "outputs_checked": {"pictures": checked_all, "mismatched_or_unknown": bad_all,
-                                "def": "md5 of every JPEG of the last timed step (all ranks) == md5 of the oracle's "
-                                       "JPEG of its stream (tests/golden/bench_manifest.json, "
-                                       "tools/make_bench_manifest.py); checked after the timed region"},
         }
+        if args.full:
+            res["outputs_verified"] = bool(manifest) and bad_all == 0
+            res["outputs_checked"] = {"pictures": checked_all, "mismatched_or_unknown": bad_all,
+                                      "def": "md5 of every JPEG of the last timed step (all ranks) == md5 of the "
+                                             "oracle's JPEG of its stream (tests/golden/bench_manifest.json, "
+                                             "tools/make_bench_manifest.py); checked after the timed region"}
         # configs[0]-style single calls: the reference fixture and one stream of this workload
-        if not args.no_single_call:
+        if args.full and not args.no_single_call:
             with open(os.path.join(ROOT, "tests", "golden", "img01.h265"), "rb") as fx:
                 fixture = fx.read()
             res["single_call_ms"] = single_call_latency([("img01.h265", fixture), ("workload_stream0", streams[0])])
         # N = 1 only: configs[1] on the SURVEY.md §8(d)-aim set (100-250 KB per picture), and the
         # end-to-end rate against the host entropy threads on this one GPU (DESIGN.md §7 predicts
         # the 1 -> 8 GPU curve from it)
-        if world == 1 and args.workload in ("hevc1080", "avc1080") and not args.no_aim:
+        if args.full and world == 1 and args.workload in ("hevc1080", "avc1080") and not args.no_aim:
             # hevc1080: `value` is already the §8(d)-aim set; the lighter round 1-5 set is value_light.
             # avc1080: value_aim = configs[2] on the 100-250 KB/picture set
             key, hkey = ("value_light", "hevc1080_light") if args.workload == "hevc1080" else ("value_aim", "avc1080_heavy")
@@ -573,7 +628,7 @@ def main():
                 if e2 is not eng:
                     e2.close()
             res["host_thread_sweep_fps"] = sweep
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(streams, host["threads"])
         print(json.dumps(res), flush=True)
     if dist is not None:

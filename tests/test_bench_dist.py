@@ -128,3 +128,49 @@ def test_verify_outputs_against_manifest():
     assert bench.verify_outputs(batch, out, offs, lens, man) == (3, 0, 1)
     out[len(j) + 100] ^= 1
     assert bench.verify_outputs(batch, out, offs, lens, man) == (3, 1, 1)
+
+
+def _fake_outputs(n, size):
+    """n 'JPEGs' of `size` bytes each, back to back with a gap, picture 2 failed."""
+    import ctypes
+    stride = size + 7
+    out = (ctypes.c_uint8 * (n * stride))()
+    offs, lens, status = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)(), (ctypes.c_int * n)()
+    for i in range(n):
+        offs[i], lens[i] = i * stride, size
+        ctypes.memmove(ctypes.addressof(out) + offs[i], bytes((i * 31 + k) & 255 for k in range(size)), size)
+    status[2], lens[2] = -7, 0
+    return out, offs, lens, status
+
+
+def test_dump_outputs_files_sample_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, status / length / CRC-32 of every picture, the
+    bytes of a seeded sample that respects the byte budget, identical from run to run."""
+    import zlib
+    import numpy as np
+    n, size = 12, 1000
+    out, offs, lens, status = _fake_outputs(n, size)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 5 * size + 10)  # room for 5 of the 11 good pictures
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), out, offs, lens, status, n)
+    bench.dump_outputs(str(b), out, offs, lens, status, n)
+    names = sorted(os.listdir(a))
+    assert names == ["jpeg_crc32.npy", "jpeg_lens.npy", "jpeg_sample_bytes.npy", "jpeg_sample_index.npy",
+                     "jpeg_status.npy"]
+    for name in names:
+        assert (a / name).read_bytes() == (b / name).read_bytes(), name
+    d = {name[:-4]: np.load(a / name) for name in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    raw = bytes(out)
+    want_len = [0 if i == 2 else size for i in range(n)]
+    assert d["jpeg_status"].tolist() == [-7 if i == 2 else 0 for i in range(n)]
+    assert d["jpeg_lens"].tolist() == want_len
+    assert d["jpeg_crc32"].tolist() == [zlib.crc32(raw[offs[i]:offs[i] + want_len[i]]) if i != 2 else 0
+                                        for i in range(n)]
+    idx = [int(i) for i in d["jpeg_sample_index"]]
+    assert len(idx) == 5 and idx == sorted(set(idx)) and 2 not in idx
+    assert d["jpeg_sample_bytes"].astype(np.uint8).tobytes() == b"".join(raw[offs[i]:offs[i] + size] for i in idx)
+    # everything fits: every good picture is dumped
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", n * size)
+    bench.dump_outputs(str(a), out, offs, lens, status, n, ".rank1")
+    assert np.load(a / "jpeg_sample_index.rank1.npy").tolist() == [i for i in range(n) if i != 2]

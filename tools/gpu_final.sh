@@ -10,8 +10,7 @@ case $2 in
 1)
   bash tools/gpu_run.sh $TAG tests smoke
   cp gpurun_out/${TAG}_tests.log gpurun_out/${TAG}_gpu_tests.txt
-  timeout -k 10 600 python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
-  tail -c 600 gpurun_out/${TAG}_bench_default.json ;;
+  bash tools/gpu_run.sh $TAG bench:hevc1080:12:--warmup,2 ;;  # the default line: python bench.py --full
 2)
   bash tools/gpu_run.sh $TAG bench:hevc1080:20 bench:avc1080:20 bench:hevc2160:10 bench:mixed:10 ;;
 ab)  # an environment A/B before the final lines: ab VAR "V1 V2" WL

@@ -7,7 +7,7 @@
 # STEP:
 #   tests[:EXPR]              -m gpu suite (EXPR: a pytest -k expression)     -> gpurun_out/TAG_tests.log
 #   smoke                     __graft_entry__.smoke()                         -> gpurun_out/TAG_smoke.log
-#   bench:WL[:STEPS[:ARGS]]   bench.py line (ARGS: extra flags, ',' for ' ')  -> gpurun_out/TAG_bench_WL.json
+#   bench:WL[:STEPS[:ARGS]]   bench.py --full line (ARGS: extra flags, ',' for ' '), as TAG_bench_WL.json
 #   kstats:WL[:ARGS[:SUF]]    rocprofv3 --kernel-trace --stats, two steps (ARGS: extra bench flags, ',' for ' ';
 #                             SUF: suffix of the output names)                -> gpurun_out/TAG_kstats_WL[SUF]/
 #   pmc:KERNEL:WL[:sq|hbm]    PMC passes of one kernel (hbm: FETCH_SIZE / WRITE_SIZE passes)
@@ -38,7 +38,7 @@ for STEP in "$@"; do
     tail -1 gpurun_out/${TAG}_smoke.log ;;
   bench)
     WL=${A1:-hevc1080}; ST=${A2:-20}; EXTRA=${A3//,/ }
-    timeout -k 10 600 python bench.py --gpus 1 --workload $WL --steps $ST --warmup 5 $EXTRA \
+    timeout -k 10 600 python bench.py --full --gpus 1 --workload $WL --steps $ST --warmup 5 $EXTRA \
       > gpurun_out/${TAG}_bench_$WL.json 2> gpurun_out/${TAG}_bench_$WL.err || { tail -20 gpurun_out/${TAG}_bench_$WL.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('$WL', round(d['value']), 'aim', d.get('value_aim'), 'us/KB', d.get('parse_core_us_per_kb'), 'hbm_res', round(d.get('hbm_resident_fps', 0)), 'frac', d['roofline']['frac'], 'verified', d.get('outputs_verified'))" gpurun_out/${TAG}_bench_$WL.json ;;
   kstats)
