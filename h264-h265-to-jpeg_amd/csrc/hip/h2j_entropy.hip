@@ -561,8 +561,9 @@ extern "C" {
 int h2j_gpu_histogram(const h2j_gpu_batch* b, void* stream) {
     if (!b || b->nframes <= 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const h2j_frame* jf = b->jframes ? b->jframes : b->frames;  // JPEG source views
     const int tiles = (b->max_mcu * 6 + kTile - 1) / kTile;
-    hipLaunchKernelGGL(h2j_k4e_dc_hist, dim3(tiles, b->nframes), dim3(kTile), 0, s, b->frames, b->arena);
+    hipLaunchKernelGGL(h2j_k4e_dc_hist, dim3(tiles, b->nframes), dim3(kTile), 0, s, jf, b->arena);
     return check(hipGetLastError(), "h2j_k4e_dc_hist");
 }
 
@@ -573,24 +574,25 @@ int h2j_gpu_entropy(const h2j_gpu_batch* b, void* stream) {
         return -1;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const h2j_frame* jf = b->jframes ? b->jframes : b->frames;  // JPEG source views
     const int tiles = (b->max_mcu * 6 + kTile - 1) / kTile;
-    hipLaunchKernelGGL(h2j_k5a_tables, dim3(4, b->nframes), dim3(64), 0, s, b->frames, b->arena);
+    hipLaunchKernelGGL(h2j_k5a_tables, dim3(4, b->nframes), dim3(64), 0, s, jf, b->arena);
     int r = check(hipGetLastError(), "h2j_k5a_tables");
     if (r) return r;
-    hipLaunchKernelGGL(h2j_k5b_tile_bits, dim3(tiles, b->nframes), dim3(kTile), 0, s, b->frames, b->arena,
+    hipLaunchKernelGGL(h2j_k5b_tile_bits, dim3(tiles, b->nframes), dim3(kTile), 0, s, jf, b->arena,
                        b->tile_bits, tiles);
     if ((r = check(hipGetLastError(), "h2j_k5b_tile_bits"))) return r;
-    hipLaunchKernelGGL(h2j_k5c_scan_tiles, dim3(b->nframes), dim3(kTile), 0, s, b->frames, b->arena, b->tile_bits,
+    hipLaunchKernelGGL(h2j_k5c_scan_tiles, dim3(b->nframes), dim3(kTile), 0, s, jf, b->arena, b->tile_bits,
                        tiles);
     if ((r = check(hipGetLastError(), "h2j_k5c_scan_tiles"))) return r;
-    hipLaunchKernelGGL(h2j_k5c_scan_frames, dim3(1), dim3(kTile), 0, s, b->frames, b->nframes, b->arena, b->seg_cap,
+    hipLaunchKernelGGL(h2j_k5c_scan_frames, dim3(1), dim3(kTile), 0, s, jf, b->nframes, b->arena, b->seg_cap,
                        b->seg_total);
     if ((r = check(hipGetLastError(), "h2j_k5c_scan_frames"))) return r;
     hipLaunchKernelGGL(h2j_k5z_zero, dim3(1024), dim3(256), 0, s, b->seg, b->seg_total);
     if ((r = check(hipGetLastError(), "h2j_k5z_zero"))) return r;
     const char* eg = std::getenv("H2J_EMIT_GLOBAL");  // read per launch: tests switch it inside one process
     const int emit_words = (eg && eg[0] == '1') ? 0 : kEmitWords;
-    hipLaunchKernelGGL(h2j_k5d_emit, dim3(tiles, b->nframes), dim3(kTile), 0, s, b->frames, b->arena, b->tile_bits,
+    hipLaunchKernelGGL(h2j_k5d_emit, dim3(tiles, b->nframes), dim3(kTile), 0, s, jf, b->arena, b->tile_bits,
                        tiles, b->seg, emit_words);
     return check(hipGetLastError(), "h2j_k5d_emit");
 }

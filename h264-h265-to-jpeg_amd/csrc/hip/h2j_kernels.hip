@@ -4548,6 +4548,126 @@ __global__ void __launch_bounds__(256, 8) h2j_k3_sao(const h2j_frame* __restrict
     else sao_ctb<uint16_t>(f, C, S, arena, ctb, L, fold);
 }
 
+// ---------------------------------------------------------------- K3s: scaled output
+// Box-filter downscale by S = 2^K of the final decoded picture (the cropped planes of pic2) into
+// the 8-bit planar picture at h2j_scaled.spic, which K4 / K5 read through the frame's JPEG source view
+// (h2j_gpu_batch.jframes).  Each plane on its own grid; output sample (x, y) of a plane of bit depth bd is
+//   min(255, (sum + (1 << (sh - 1))) >> sh),  sh = 2K + bd - 8,
+// sum over the S x S source samples at (x S + i, y S + j), coordinates clamped to the cropped
+// plane's last column / row (the edge replication of the JPEG padding, jpeg_sample).
+// A read-once stream: a workgroup is 4 output rows of 64 dwords, a lane makes 4 adjacent output
+// samples (one dword store) from S rows of 4S source samples, so a wave reads S contiguous row
+// segments of 256 S sizeof(Pel) bytes.  Rows are loaded 8 or 16 bytes at a time where the crop and
+// the row pitch keep them aligned and the 4S columns lie inside the plane (rows clamp there too:
+// a clamped row is the same load again); the other lanes -- the right edge, unaligned crops --
+// sum clamped single samples.
+DEVI uint32_t k3s_pk_add_u16(uint32_t a, uint32_t b) {  // v_pk_add_u16
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b));
+}
+template <int NW>
+DEVI void k3s_load_row(const void* p, uint32_t (&w)[NW]) {
+    if constexpr (NW == 2) {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        w[0] = v.x;
+        w[1] = v.y;
+    } else {
+#pragma unroll
+        for (int q = 0; q < NW / 4; q++) {
+            const uint4 v = reinterpret_cast<const uint4*>(p)[q];
+            w[4 * q] = v.x;
+            w[4 * q + 1] = v.y;
+            w[4 * q + 2] = v.z;
+            w[4 * q + 3] = v.w;
+        }
+    }
+}
+template <typename Pel, int K>
+__global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
+                                                         const h2j_scaled* __restrict__ smap) {
+    constexpr int S = 1 << K;
+    constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;  // dwords of one source row of a lane
+    constexpr int LW = NW == 2 ? 8 : 16;                            // bytes per load
+    // workgroup order, timed both ways on 1024 1080p pictures (profiles/scale_k3s_order_ab.md): the
+    // XCD-aware order wins at K = 1 (0.97 against 1.01 ms), the dispatcher's own order at K = 2 and 3
+    // (0.58 against 0.62 and 0.61 ms) -- as grid.h records for the other read-once streams
+    const GridPos gp = K == 1 ? xcd_grid_pos() : GridPos{static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y)};
+    const h2j_scaled& sc = smap[gp.y];
+    const h2j_frame& f = frames[sc.frame];
+    if (sc.scale_log2 != K || (f.bit_depth > 8) != (sizeof(Pel) == 2)) return;
+    // K3 SAO may have summed this picture's unscaled MB variances (h2j_sao_folds_variance does not know
+    // of scaling): the rate control wants those of the scaled picture, which K4a sums after this kernel
+    if (gp.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + f.jstat)->var_sum = 0;
+    const int tl = h2j_k3s_plane_tiles(sc.jpeg_w, sc.jpeg_h), tc = h2j_k3s_plane_tiles(sc.jpeg_w >> 1, sc.jpeg_h >> 1);
+    int t = gp.x, c = 0;
+    if (t >= tl + 2 * tc) return;
+    if (t >= tl) {
+        t -= tl;
+        c = 1;
+        if (t >= tc) {
+            t -= tc;
+            c = 2;
+        }
+    }
+    const int shc = c ? 1 : 0;
+    const int ow = sc.jpeg_w >> shc, oh = sc.jpeg_h >> shc;  // scaled plane
+    const int dw = (ow + 3) >> 2, tx = (dw + 63) >> 6;
+    const int xd = (t % tx) * 64 + static_cast<int>(threadIdx.x & 63), y = (t / tx) * 4 + static_cast<int>(threadIdx.x >> 6);
+    if (xd >= dw || y >= oh) return;
+    const int pw = f.out_w >> shc, ph = f.out_h >> shc;    // cropped source plane
+    const int cx = f.crop_x >> shc, cy = f.crop_y >> shc, st = f.pic_stride[c];
+    const int bd = c ? f.bit_depth_c : f.bit_depth, sh = 2 * K + bd - 8;
+    const Pel* P = reinterpret_cast<const Pel*>(arena + f.pic2) + f.pic_off[c];
+    const int xs = xd * 4 * S;  // first source column of this lane
+    // uniform over the plane: its first cropped sample and its row pitch are load-aligned (xs is)
+    const bool aligned = (((static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) |
+                           (static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel)))) & (LW - 1)) == 0;
+    unsigned acc[4] = {0, 0, 0, 0};
+    if (aligned && xs + 4 * S <= pw) {
+        if constexpr (sizeof(Pel) == 1) {
+            uint32_t w[S][NW];
+#pragma unroll
+            for (int j = 0; j < S; j++) k3s_load_row<NW>(at32(P, m24(min(y * S + j, ph - 1) + cy, st) + cx + xs), w[j]);
+#pragma unroll
+            for (int j = 0; j < S; j++)
+#pragma unroll
+                for (int o = 0; o < 4; o++) {  // S bytes per output: half a dword, one, two
+                    if constexpr (K == 1) acc[o] = __builtin_amdgcn_udot4(w[j][o >> 1], (o & 1) ? 0x01010000u : 0x00000101u, acc[o], false);
+                    else if constexpr (K == 2) acc[o] = __builtin_amdgcn_udot4(w[j][o], 0x01010101u, acc[o], false);
+                    else acc[o] = __builtin_amdgcn_udot4(w[j][2 * o], 0x01010101u,
+                                                         __builtin_amdgcn_udot4(w[j][2 * o + 1], 0x01010101u, acc[o], false), false);
+                }
+        } else {
+            // rows add up as packed 16-bit pairs, four rows at most (4 x (2^14 - 1) < 2^16: bit depths to 14)
+            constexpr int G = S < 4 ? S : 4;
+#pragma unroll
+            for (int g = 0; g < S; g += G) {
+                uint32_t w[G][NW];
+#pragma unroll
+                for (int j = 0; j < G; j++) k3s_load_row<NW>(at32(P, m24(min(y * S + g + j, ph - 1) + cy, st) + cx + xs), w[j]);
+#pragma unroll
+                for (int q = 0; q < NW; q++) {
+                    uint32_t pk = w[0][q];
+#pragma unroll
+                    for (int j = 1; j < G; j++) pk = k3s_pk_add_u16(pk, w[j][q]);
+                    acc[q / (S / 2)] += (pk & 0xFFFFu) + (pk >> 16);  // S / 2 dwords per output
+                }
+            }
+        }
+    } else {
+        for (int o = 0; o < 4; o++)
+            for (int j = 0; j < S; j++) {
+                const int ro = m24(min(y * S + j, ph - 1) + cy, st) + cx;
+                for (int i = 0; i < S; i++) acc[o] += static_cast<unsigned>(*at32(P, ro + min(xs + o * S + i, pw - 1)));
+            }
+    }
+    uint32_t out = 0;
+#pragma unroll
+    for (int o = 0; o < 4; o++) out |= min((acc[o] + (1u << (sh - 1))) >> sh, 255u) << (8 * o);
+    // the row pitch holds whole 16-byte groups: the last dword of a row may run into its padding
+    *reinterpret_cast<uint32_t*>(arena + sc.spic + sc.spic_off[c] + static_cast<uint32_t>(m24(y, sc.spic_stride[c]) + 4 * xd)) = out;
+}
+
 // ---------------------------------------------------------------- K4: JPEG
 template <typename Pel>
 DEVI int jpeg_sample(const h2j_frame& f, const uint8_t* arena, int c, int x, int y) {
@@ -5375,25 +5495,47 @@ int h2j_gpu_sao(const h2j_gpu_batch* b, void* stream) {
     return 0;
 }
 
+int h2j_gpu_scale(const h2j_gpu_batch* b, void* stream) {
+    if (!b || b->nframes <= 0 || !b->scale_map) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // one launch per (sample type, scale) class present: grid = the class's largest picture x its pictures
+    for (int cls = 0; cls < H2J_SCALE_CLASSES; cls++) {
+        if (b->scale_count[cls] <= 0 || b->scale_tiles[cls] <= 0) continue;
+        const dim3 grid(static_cast<unsigned>(b->scale_tiles[cls]), static_cast<unsigned>(b->scale_count[cls]));
+        const h2j_scaled* map = b->scale_map + b->scale_first[cls];
+        switch (cls) {
+        case 0: hipLaunchKernelGGL((h2j_k3s_downscale<uint8_t, 1>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 1: hipLaunchKernelGGL((h2j_k3s_downscale<uint8_t, 2>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 2: hipLaunchKernelGGL((h2j_k3s_downscale<uint8_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 3: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 1>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 4: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 2>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        default: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        }
+        if (int rc = check(hipGetLastError(), "h2j_k3s_downscale")) return rc;
+    }
+    return 0;
+}
+
 int h2j_gpu_jpeg(const h2j_gpu_batch* b, void* stream) {
     if (!b || b->nframes <= 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const h2j_frame* jf = b->jframes ? b->jframes : b->frames;  // JPEG source views
     const int mbs = b->max_mcu;
     if (b->k4a_frames > 0) {  // none: K3 has summed every picture's MB variances
-        hipLaunchKernelGGL(h2j_k4a_variance, dim3((mbs + 15) / 16, b->nframes), dim3(256), 0, s, b->frames, b->arena, 1);
+        hipLaunchKernelGGL(h2j_k4a_variance, dim3((mbs + 15) / 16, b->nframes), dim3(256), 0, s, jf, b->arena, 1);
         const int r = check(hipGetLastError(), "h2j_k4a_variance");
         if (r) return r;
     }
     int r = 0;
-    hipLaunchKernelGGL(h2j_k4b_ratecontrol, dim3(b->nframes), dim3(64), 0, s, b->frames, b->arena);
+    hipLaunchKernelGGL(h2j_k4b_ratecontrol, dim3(b->nframes), dim3(64), 0, s, jf, b->arena);
     r = check(hipGetLastError(), "h2j_k4b_ratecontrol");
     if (r) return r;
     const int nblk = mbs * 6;
     if (b->jpeg_dense) {  // inspection path (h2j_engine_jpeg_coeffs): the dense int16 plane
-        hipLaunchKernelGGL(h2j_k4c_fdct_quant, dim3((nblk + 255) / 256, b->nframes), dim3(256), 0, s, b->frames, b->arena);
+        hipLaunchKernelGGL(h2j_k4c_fdct_quant, dim3((nblk + 255) / 256, b->nframes), dim3(256), 0, s, jf, b->arena);
         return check(hipGetLastError(), "h2j_k4c_fdct_quant");
     }
-    hipLaunchKernelGGL(h2j_k4c_fdct_sym, dim3((nblk + 255) / 256, b->nframes), dim3(256), 0, s, b->frames, b->arena);
+    hipLaunchKernelGGL(h2j_k4c_fdct_sym, dim3((nblk + 255) / 256, b->nframes), dim3(256), 0, s, jf, b->arena);
     r = check(hipGetLastError(), "h2j_k4c_fdct_sym");
     if (r) return r;
     return h2j_gpu_histogram(b, stream);  // DC histograms

@@ -53,6 +53,7 @@ namespace {
 struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
+    h2j_out_opts opts = {0, 0};  // scaled output (h2j_h265_to_jpeg_mem_scaled); {0, 0}: the decoded size
     std::vector<uint8_t> jpeg;
     int status = 0;
     std::string error;
@@ -116,8 +117,10 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> sizes(n), off(n), len(n);
     std::vector<int> status(n);
+    std::vector<h2j_out_opts> opts(n);
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
+        opts[i] = batch[i]->opts;
         ptrs[i] = batch[i]->data;
         sizes[i] = batch[i]->size;
         cap += batch[i]->size * 4 + (2u << 20);
@@ -126,8 +129,8 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = h2j_engine_transcode(e, n, ptrs.data(), sizes.data(), out.data(), cap, off.data(), len.data(),
-                                 status.data());
+        r = h2j_engine_transcode_opts(e, n, ptrs.data(), sizes.data(), opts.data(), out.data(), cap, off.data(),
+                                      len.data(), status.data());
         bool small = false;
         for (int i = 0; i < n; i++) small = small || status[i] == -50;
         if (!small) break;
@@ -256,6 +259,11 @@ std::shared_ptr<IDecoder> IDecoder::getInstance() { return std::make_shared<Deco
 // ---- in-memory and batch entry points beside IDecoder
 
 extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** jpeg, size_t* jpeg_len) {
+    return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int scale_log2, int max_dim, uint8_t** jpeg,
+                                           size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
     *jpeg = nullptr;
     *jpeg_len = 0;
@@ -263,6 +271,8 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     Request req;
     req.data = data;
     req.size = size;
+    req.opts.scale_log2 = scale_log2;
+    req.opts.max_dim = max_dim;
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;

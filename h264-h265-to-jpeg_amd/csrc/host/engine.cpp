@@ -177,14 +177,55 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
+// Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
+// max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does)
+bool out_opts_valid(const h2j_out_opts& o) { return o.scale_log2 >= 0 && o.scale_log2 <= 3 && o.max_dim >= 0; }
+int resolve_scale(const h2j_out_opts& o, int w, int h) {
+    int k = o.scale_log2;
+    if (o.max_dim > 0)
+        while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
+    return k;
+}
+// parse one item of a batch with its output options; invalid options fail the item alone
+int parse_item(const uint8_t* d, size_t n, const h2j_out_opts& o, FrameJob& job) {
+    if (!out_opts_valid(o)) {
+        job.clear();
+        job.error = H2J_ERR_OUT_OPTS;
+        job.message = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
+                      std::to_string(o.max_dim) + " (>= 0)";
+        return job.error;
+    }
+    const int r = parse_any(d, n, job);
+    if (r == 0) job.scale_log2 = resolve_scale(o, job.hdr.out_w, job.hdr.out_h);  // needs the parsed size
+    return r;
+}
+
+// The JPEG source view of a frame: what K4 (variance, FDCT) and K5 read as "the picture"
+// (include/h2j_gpu.h h2j_gpu_batch.jframes).  An unscaled frame is its own view; a scaled frame's
+// view is the 8-bit picture K3s writes at its h2j_scaled record's spic.
+h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc) {
+    h2j_frame v = f;
+    if (sc.scale_log2 == 0) return v;
+    v.pic = v.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
+    v.crop_x = v.crop_y = 0;
+    v.out_w = sc.jpeg_w;
+    v.out_h = sc.jpeg_h;
+    v.bit_depth = v.bit_depth_c = 8;
+    for (int c = 0; c < 3; c++) {
+        v.pic_stride[c] = sc.spic_stride[c];
+        v.pic_off[c] = sc.spic_off[c];
+    }
+    return v;
+}
+
 }  // namespace
 
 // One in-flight chunk: its stream, buffers and layout.
 struct Slot {
     void* stream = nullptr;
     // 9: after the stats D2H, 10 / 11: around the in-stream payload D2H, 12 / 13: around the wait for
-    // the other slot, 14 / 15: around a second (whole) payload copy
-    void* ev[16] = {nullptr};
+    // the other slot, 14 / 15: around a second (whole) payload copy, 16: after K3s (scaled output)
+    void* ev[17] = {nullptr};
     size_t pay_pre = 0;        // payload bytes already copied in-stream by enqueue() (estimated, <= h_seg's capacity)
     double px = 0;             // output pixels of the chunk (payload estimate)
     int small_runs = 0;        // consecutive chunks whose payload used < 1/4 of h_seg (shrink after 8)
@@ -192,6 +233,7 @@ struct Slot {
     DevBuf d_in, d_arena, d_seg, d_scratch;
     HostBuf h_in, h_js, h_seg;
     std::vector<h2j_frame> frames;
+    std::vector<h2j_scaled> scaled;  // per frame: its JPEG size and, for a scaled picture, its scaled planes
     std::vector<int> live;  // job index of each frame of the chunk
     std::vector<FrameJob>* jobs = nullptr;  // the job set `live` indexes
     h2j_gpu_batch batch{};
@@ -223,7 +265,7 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_N };  // ST_PACK: host time packing records into staging
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s
 
 // H.264 pictures with more MB rows than this are reconstructed by several K1 workgroups
 constexpr int kK1BandRows = 68;
@@ -247,6 +289,7 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
+    std::vector<h2j_out_opts> opts;            // per-item output options (empty: all {0, 0})
     std::vector<int> bounds;                   // parse chunks: index ranges
     std::vector<int> chunk_of;
     std::unique_ptr<std::atomic<int>[]> left;  // pictures of each parse chunk still being parsed
@@ -359,6 +402,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     s.pending = false;
     if (nf == 0) return 0;
     s.frames.resize(nf);
+    s.scaled.resize(nf);
     size_t ntu = 0, ncoef = 0, nctb = 0, nslice = 0, nsl = 0, nblk = 0;
     int max_w = 0, max_h = 0, max_mcu = 0, max_ntu = 0, max_ctbs = 0;
     const std::vector<FrameJob>& jobs = *s.jobs;
@@ -383,15 +427,22 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
         f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
         f.xline = 0;
+        // the JPEG's size: the cropped picture, or its scaled size (K4 / K5 work on that picture)
+        h2j_scaled sc{};
+        sc.frame = k;
+        sc.scale_log2 = j.scale_log2;
+        sc.jpeg_w = h2j_scaled_dim(f.out_w, sc.scale_log2);
+        sc.jpeg_h = h2j_scaled_dim(f.out_h, sc.scale_log2);
+        s.scaled[k] = sc;
         s.frames[k] = f;
         max_w = std::max(max_w, f.width);
         if (f.codec == H2J_CODEC_HEVC) max_ctbs = std::max(max_ctbs, f.ctb_w * f.ctb_h);
         max_h = std::max(max_h, f.height);
-        const int mcu = ((f.out_w + 15) >> 4) * ((f.out_h + 15) >> 4);
+        const int mcu = ((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4);
         max_mcu = std::max(max_mcu, mcu);
         nblk += static_cast<size_t>(mcu) * 6;
     }
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][jcoef][res][aux]
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
     size_t off = 0;
     for (int k = 0; k < nf; k++) {
         h2j_frame& f = s.frames[k];
@@ -424,11 +475,26 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
             if (pass == 0) f.pic = off; else f.pic2 = off;
             off = align_up(off + (ysz + 2 * csz) * pel, 256);
         }
+    int nscaled = 0;
+    for (int k = 0; k < nf; k++) {  // the 8-bit scaled planes K3s writes and K4 reads (scaled pictures only)
+        h2j_scaled& sc = s.scaled[k];
+        if (sc.scale_log2 == 0) continue;
+        nscaled++;
+        sc.spic = off;
+        size_t po = 0;
+        for (int c = 0; c < 3; c++) {
+            const int pw = c ? sc.jpeg_w / 2 : sc.jpeg_w, ph = c ? sc.jpeg_h / 2 : sc.jpeg_h;
+            sc.spic_stride[c] = h2j_spic_stride(pw);
+            sc.spic_off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(sc.spic_stride[c]) * ph;
+        }
+        off = align_up(off + po, 256);
+    }
     s.jcoef_base = off;
     for (int k = 0; k < nf; k++) {  // dense int16 plane (inspection) or the JPEG symbol tiles
         h2j_frame& f = s.frames[k];
         f.jcoef = off;
-        const size_t blocks = static_cast<size_t>(((f.out_w + 15) >> 4) * ((f.out_h + 15) >> 4)) * 6;
+        const size_t blocks = static_cast<size_t>(((s.scaled[k].jpeg_w + 15) >> 4) * ((s.scaled[k].jpeg_h + 15) >> 4)) * 6;
         off = align_up(off + std::max(blocks * 64 * 2, (blocks + 255) / 256 * static_cast<size_t>(H2J_JTILE_BYTES)), 256);
     }
     s.jcoef_bytes = off - s.jcoef_base;
@@ -557,12 +623,29 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
             saomap.push_back(e[i].second);
         }
     }
+    // K3s map: the scaled pictures by class (sample type x scale), one launch per class present,
+    // its grid as wide as the class's largest picture needs
+    std::vector<h2j_scaled> scalemap;
+    int sc_first[H2J_SCALE_CLASSES] = {}, sc_count[H2J_SCALE_CLASSES] = {}, sc_tiles[H2J_SCALE_CLASSES] = {};
+    for (int cls = 0; cls < H2J_SCALE_CLASSES && nscaled; cls++) {
+        sc_first[cls] = static_cast<int>(scalemap.size());
+        for (int k = 0; k < nf; k++) {
+            const h2j_scaled& sc = s.scaled[k];
+            if (sc.scale_log2 == 0 || 3 * (s.frames[k].bit_depth > 8 ? 1 : 0) + sc.scale_log2 - 1 != cls) continue;
+            scalemap.push_back(sc);
+            sc_count[cls]++;
+            sc_tiles[cls] = std::max(sc_tiles[cls], h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
+        }
+    }
     const size_t o_map = align_up(o_sl + nsl + 16, 256);
     const size_t o_all = align_up(o_map + k1map.size() * 4 + 16, 256);
     const size_t o_sao = align_up(o_all + k1all.size() * 4 + 16, 256);
     const size_t o_map8 = align_up(o_sao + saomap.size() * 4 + 16, 256);
     const size_t o_hev = align_up(o_map8 + k1map8.size() * 4 + 16, 256);
-    const size_t in_bytes = align_up(o_hev + k1hevc.size() * 4 + 16, 256);
+    // scaled pictures present: the JPEG source views of all frames and the K3s map follow
+    const size_t o_jfr = align_up(o_hev + k1hevc.size() * 4 + 16, 256);
+    const size_t o_scl = nscaled ? align_up(o_jfr + nf * sizeof(h2j_frame), 256) : o_jfr;
+    const size_t in_bytes = nscaled ? align_up(o_scl + scalemap.size() * sizeof(h2j_scaled) + 16, 256) : o_jfr;
     if (!s.h_in.ensure(in_bytes)) return fail("pinned host allocation failed");
     if (!s.d_in.ensure(in_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
     if (!s.d_arena.ensure(arena_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
@@ -580,6 +663,11 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     if (!saomap.empty()) std::memcpy(s.h_in.p + o_sao, saomap.data(), saomap.size() * 4);
     if (!k1map8.empty()) std::memcpy(s.h_in.p + o_map8, k1map8.data(), k1map8.size() * 4);
     if (!k1hevc.empty()) std::memcpy(s.h_in.p + o_hev, k1hevc.data(), k1hevc.size() * 4);
+    if (nscaled) {
+        h2j_frame* jv = reinterpret_cast<h2j_frame*>(s.h_in.p + o_jfr);
+        for (int k = 0; k < nf; k++) jv[k] = jpeg_view(s.frames[k], s.scaled[k]);
+        std::memcpy(s.h_in.p + o_scl, scalemap.data(), scalemap.size() * sizeof(h2j_scaled));
+    }
     std::vector<size_t> bt(nf), bc(nf), bk(nf), bs(nf), bl(nf);
     {
         size_t a = 0, b = 0, c = 0, d = 0, e = 0;
@@ -643,6 +731,13 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         b.sao_count[g] = sao_count[g];
         b.sao_ctbs[g] = sao_ctbs[g];
     }
+    b.jframes = nscaled ? reinterpret_cast<const h2j_frame*>(din + o_jfr) : b.frames;
+    b.scale_map = nscaled ? reinterpret_cast<const h2j_scaled*>(din + o_scl) : nullptr;
+    for (int c = 0; c < H2J_SCALE_CLASSES; c++) {
+        b.scale_first[c] = sc_first[c];
+        b.scale_count[c] = sc_count[c];
+        b.scale_tiles[c] = sc_tiles[c];
+    }
     b.hevc_pels = 0;
     for (int k = 0; k < nf; k++)
         if (s.frames[k].codec == H2J_CODEC_HEVC) b.hevc_pels |= (s.frames[k].bit_depth > 8 || s.frames[k].bit_depth_c > 8) ? 2 : 1;
@@ -650,7 +745,8 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     b.jpeg_dense = entropy ? 0 : 1;
     {  // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
         int k4a = 0;
-        for (int k = 0; k < nf; k++) k4a += h2j_sao_folds_variance(s.frames[k]) ? 0 : 1;
+        // (a scaled picture: always K4a, on the scaled picture; K3s clears what K3 may have summed)
+        for (int k = 0; k < nf; k++) k4a += (h2j_sao_folds_variance(s.frames[k]) && s.scaled[k].scale_log2 == 0) ? 0 : 1;
         b.k4a_frames = k4a;
     }
     b.seg = entropy ? static_cast<uint8_t*>(s.d_seg.p) : nullptr;
@@ -680,6 +776,8 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     h2j_gpu_event_record(s.ev[3], st);
     if (stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[4], st);
+    if (stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s: no launch without scaled pictures
+    h2j_gpu_event_record(s.ev[16], st);
     if (stages >= 4 && h2j_gpu_jpeg(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[5], st);
     if (entropy && h2j_gpu_entropy(&b, st)) return drain_fail(s, h2j_gpu_last_error());
@@ -707,7 +805,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     }
     s.pay_pre = 0;
     s.px = 0;
-    for (int k = 0; k < nf; k++) s.px += static_cast<double>(s.frames[k].out_w) * s.frames[k].out_h;
+    for (int k = 0; k < nf; k++) s.px += static_cast<double>(s.scaled[k].jpeg_w) * s.scaled[k].jpeg_h;  // JPEG pixels
     if (entropy && s.h_seg.cap > 0) {
         // the copy is sized by the engine's payload-per-pixel estimate (1.3x, 4 KB
         // granules), not by the buffer's high-water mark: a small chunk after a 4K one moves its own
@@ -772,7 +870,8 @@ int Engine::sync(Slot& s) {
     stats[ST_CHUNKS] += 1;
     stats[ST_DEBLOCK] += h2j_gpu_event_elapsed_ms(s.ev[2], s.ev[3]);
     stats[ST_SAO] += h2j_gpu_event_elapsed_ms(s.ev[3], s.ev[4]);
-    stats[ST_JPEG] += h2j_gpu_event_elapsed_ms(s.ev[4], s.ev[5]);
+    stats[ST_SCALE] += h2j_gpu_event_elapsed_ms(s.ev[4], s.ev[16]);
+    stats[ST_JPEG] += h2j_gpu_event_elapsed_ms(s.ev[16], s.ev[5]);
     stats[ST_ENTROPY] += h2j_gpu_event_elapsed_ms(s.ev[5], s.ev[6]);
     // copies only (the payload copy is enqueued once the host has read the sizes)
     const double d2h_stats = h2j_gpu_event_elapsed_ms(s.ev[6], s.ev[9]);
@@ -836,7 +935,8 @@ constexpr double kSlotHbmBudget = 64e9;  // at most, per slot (two slots per eng
 constexpr int kMaxGpuChunk = 1024;
 static double hbm_estimate(const FrameJob& j) {
     const double px = static_cast<double>(j.hdr.width) * j.hdr.height;
-    return px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + (1 << 20);
+    // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample; its JPEG regions shrink by more)
+    return px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + (j.scale_log2 ? 1.5 * px / (1 << 2 * j.scale_log2) : 0.0) + (1 << 20);
 }
 
 void Engine::start_threads() {
@@ -877,7 +977,7 @@ void Engine::parse_loop() {
             pool->parallel_for(b->n, [&](int k) {
                 const int i = order[static_cast<size_t>(k)];
                 jobs[i].threads = slice_threads;
-                parse_any(b->data[i], b->sizes[i], jobs[i]);
+                parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts{0, 0} : b->opts[static_cast<size_t>(i)], jobs[i]);
                 if (b->left[b->chunk_of[i]].fetch_sub(1) == 1) {
                     std::lock_guard<std::mutex> g2(amu);
                     acv.notify_all();
@@ -977,8 +1077,8 @@ int Engine::run_batch(Batch& b) {
         auto write = [&](int k) {
             if (at[k] == ~static_cast<size_t>(0)) return;
             const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
-            const h2j_frame& f = s.frames[k];
-            jpeg_write_container(*st, s.h_seg.p + st->seg_off, f.out_w, f.out_h, kLavcIdent, b.out + at[k]);
+            const h2j_scaled& sc = s.scaled[k];
+            jpeg_write_container(*st, s.h_seg.p + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[k]);
         };
         par(nf, write);
         stats[ST_ASSEMBLE] += now_ms() - ta;
@@ -1109,8 +1209,9 @@ void h2j_engine_destroy(h2j_engine* e) { delete e; }
 const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no engine"; }
 
 // submit one batch; latency: the synchronous plan (small tail chunks), else the throughput plan
-static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* out,
-                            size_t out_cap, size_t* out_off, size_t* out_len, int* status, bool latency) {
+static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
+                            const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
     b->n = n;
@@ -1121,6 +1222,7 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     b->out_off = out_off;
     b->out_len = out_len;
     b->status = status;
+    if (opts) b->opts.assign(opts, opts + n);
     for (int i = 0; i < n; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
@@ -1149,7 +1251,14 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
 int64_t h2j_engine_submit(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* out,
                           size_t out_cap, size_t* out_off, size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, out, out_cap, out_off, out_len, status, false);
+}
+
+int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
+                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                               int* status) {
+    if (!w || n < 0) return -1;
+    return submit_batch(w, n, data, sizes, opts, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1174,7 +1283,15 @@ int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
 int h2j_engine_transcode(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* out,
                          size_t out_cap, size_t* out_off, size_t* out_len, int* status) {
     if (!w) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
+                              const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                              int* status) {
+    if (!w || n < 0) return -1;
+    const int64_t t = submit_batch(w, n, data, sizes, opts, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1277,6 +1394,54 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
     info[1] = f.out_h;
     info[2] = st.qscale;
     info[3] = nmcu;
+    return 0;
+}
+
+int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
+                             uint8_t* planes_out, size_t cap, int* info) {
+    if (!w || !data || !planes_out || !info) return -1;
+    Engine& e = w->e;
+    const h2j_out_opts o = {scale_log2, max_dim};
+    if (!h2j::out_opts_valid(o)) {
+        e.fail("invalid output options");
+        return H2J_ERR_OUT_OPTS;
+    }
+    if (single_job(w, data, size)) return -2;
+    e.jobs[0].scale_log2 = h2j::resolve_scale(o, e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h);
+    Slot& s = e.slot[0];
+    if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
+    // the picture K4 would read: the frame's JPEG source view
+    const h2j_frame& f = s.frames[0];
+    const h2j_scaled& sc = s.scaled[0];
+    const h2j_frame v = h2j::jpeg_view(f, sc);
+    const int w_ = v.out_w, h_ = v.out_h;
+    info[0] = w_;
+    info[1] = h_;
+    info[2] = sc.scale_log2;
+    info[3] = f.bit_depth;
+    if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
+    const size_t pel = v.bit_depth > 8 ? 2 : 1;
+    size_t bytes = 0;  // the view's planes in the arena, from v.pic2
+    for (int c = 0; c < 3; c++) {
+        const int rows = sc.scale_log2 ? (h_ >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
+        bytes = std::max(bytes, (static_cast<size_t>(v.pic_off[c]) + static_cast<size_t>(v.pic_stride[c]) * rows) * pel);
+    }
+    std::vector<uint8_t> tmp(bytes);
+    if (h2j_gpu_memcpy_d2h(tmp.data(), static_cast<uint8_t*>(s.d_arena.p) + v.pic2, bytes, s.stream) ||
+        h2j_gpu_stream_sync(s.stream))
+        return e.fail(h2j_gpu_last_error());
+    size_t o_ = 0;
+    for (int c = 0; c < 3; c++) {
+        const int sh = c ? 1 : 0, bd = c ? v.bit_depth_c : v.bit_depth;
+        for (int y = 0; y < (h_ >> sh); y++)
+            for (int x = 0; x < (w_ >> sh); x++) {
+                const size_t idx = static_cast<size_t>(v.pic_off[c]) +
+                                   static_cast<size_t>(y + (v.crop_y >> sh)) * v.pic_stride[c] + x + (v.crop_x >> sh);
+                int val = pel == 1 ? tmp[idx] : reinterpret_cast<const uint16_t*>(tmp.data())[idx];
+                if (bd > 8) val = std::min(255, (val + (1 << (bd - 9))) >> (bd - 8));  // K4's conversion (jpeg_sample)
+                planes_out[o_++] = static_cast<uint8_t>(val);
+            }
+    }
     return 0;
 }
 

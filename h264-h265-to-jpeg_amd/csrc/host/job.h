@@ -26,6 +26,9 @@ struct FrameJob {
     // the second field; the reference sends one packet (one field) and returns false (only
     // H2J_STRICT_REFERENCE acts on it)
     bool field_pair = false;
+    // scaled output: the JPEG at 1/2^scale_log2 of the decoded size (the engine sets it after the
+    // parse, from the item's output options and the parsed size)
+    int scale_log2 = 0;
 
     void clear() {
         hdr = h2j_frame{};
@@ -38,6 +41,7 @@ struct FrameJob {
         message.clear();
         reorder_delay = false;
         field_pair = false;
+        scale_log2 = 0;
     }
 };
 

@@ -19,6 +19,14 @@ _LIB_NAME = "libH265ToJpeg.so"
 _lib = None
 
 
+class OutOpts(ctypes.Structure):
+    """include/h2j.h h2j_out_opts: per-item scaled output."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32)]
+
+
+ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
+
+
 def lib_path() -> str:
     # H2J_LIB_DIR selects an alternative build of the same libraries (e.g. build/prof)
     return os.path.join(os.environ.get("H2J_LIB_DIR", _HERE), _LIB_NAME)
@@ -56,6 +64,22 @@ def load_library() -> ctypes.CDLL:
     lib.h2j_engine_submit.restype = ctypes.c_int64
     lib.h2j_engine_submit.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, u8p,
                                       ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+    # scaled output; an older build selected through H2J_LIB_DIR (same-box A/B runs) lacks these
+    # symbols and still loads -- a scaled call on it fails with AttributeError
+    if hasattr(lib, "h2j_engine_transcode_opts"):
+        optp = ctypes.POINTER(OutOpts)
+        lib.h2j_engine_transcode_opts.restype = ctypes.c_int
+        lib.h2j_engine_transcode_opts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, optp, u8p,
+                                                  ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_opts.restype = ctypes.c_int64
+        lib.h2j_engine_submit_opts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, optp, u8p,
+                                               ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_decode_scaled.restype = ctypes.c_int
+        lib.h2j_engine_decode_scaled.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_scaled.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_scaled.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u8p), szp]
+    lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
     lib.h2j_engine_stats.restype = ctypes.c_int
@@ -85,7 +109,27 @@ def _u8(buf: bytes):
 STAT_KEYS = ["parse_ms", "h2d_ms", "recon_ms", "deblock_ms", "sao_ms", "jpeg_ms", "d2h_ms",
              "assemble_ms", "total_ms", "frames", "alg_bytes", "entropy_ms", "prep_ms", "chunks", "pack_ms",
              "parse_run_ms", "d2h_stats_ms", "d2h_payload_ms", "payload_bytes", "host_grow_ms", "h2d_bytes",
-             "payload_copied_bytes"]
+             "payload_copied_bytes", "scale_ms"]
+
+
+def _per_item(v, n, name):
+    """A scalar or a per-item sequence of n ints (None: 0)."""
+    if v is None:
+        return [0] * n
+    if isinstance(v, (int, np.integer)):
+        return [int(v)] * n
+    v = [int(x) for x in v]
+    if len(v) != n:
+        raise ValueError(f"{name}: {len(v)} entries for {n} streams")
+    return v
+
+
+def _out_opts(scale, max_dim, n):
+    """ctypes h2j_out_opts[n], or None (the unscaled call) when neither keyword is given."""
+    if scale is None and max_dim is None:
+        return None
+    sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
+    return (OutOpts * n)(*[OutOpts(a, b) for a, b in zip(sc, md)])
 
 
 class Engine:
@@ -93,6 +137,7 @@ class Engine:
 
     def __init__(self, device: int = 0, host_threads: int = 0):
         self._lib = load_library()
+        self.last_status: List[int] = []
         self._h = self._lib.h2j_engine_create(int(device), int(host_threads))
         if not self._h:
             raise RuntimeError("h2j_engine_create failed: no usable HIP device for the MI355X pipeline")
@@ -121,11 +166,17 @@ class Engine:
         self._lib.h2j_engine_host_info(self._h, arr, 4)
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
-    def transcode(self, streams: Sequence[bytes]) -> List[Optional[bytes]]:
-        """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed)."""
+    def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None) -> List[Optional[bytes]]:
+        """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
+
+        scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
+        smallest scale from `scale` up whose JPEG is at most max_dim wide and high) are scalars
+        or per-item sequences (include/h2j.h h2j_out_opts); the same stream may be listed several
+        times with different scales."""
         n = len(streams)
         if n == 0:
             return []
+        opts = _out_opts(scale, max_dim, n)
         bufs = [_u8(s) for s in streams]
         ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
@@ -136,12 +187,16 @@ class Engine:
         status = (ctypes.c_int * n)()
         for _ in range(4):
             out = (ctypes.c_uint8 * cap)()
-            rc = self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+            if opts is None:
+                rc = self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+            else:
+                rc = self._lib.h2j_engine_transcode_opts(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
             if not any(status[i] == -50 for i in range(n)):
                 break
             cap *= 4
         if rc < 0 and rc != -3:
             raise RuntimeError(f"h2j_engine_transcode failed ({rc}): {self.error()}")
+        self.last_status = [int(status[i]) for i in range(n)]  # per-item status of this call
         mv = memoryview(out)
         return [bytes(mv[offs[i]:offs[i] + lens[i]]) if status[i] == 0 else None for i in range(n)]
 
@@ -149,10 +204,13 @@ class Engine:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
         return self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
 
-    def submit_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
+    def submit_raw(self, ptrs, sizes, n, out, cap, offs, lens, status, opts=None) -> int:
         """Asynchronous batch (h2j_engine_submit): returns a ticket; the ctypes arrays must stay
-        alive until wait(ticket)."""
-        t = self._lib.h2j_engine_submit(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+        alive until wait(ticket).  opts: h2j_out_opts[n] (h2j_engine_submit_opts) or None."""
+        if opts is None:
+            t = self._lib.h2j_engine_submit(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+        else:
+            t = self._lib.h2j_engine_submit_opts(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
         if t <= 0:
             raise RuntimeError(f"h2j_engine_submit failed ({t})")
         return t
@@ -160,11 +218,20 @@ class Engine:
     def wait(self, ticket: int) -> int:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
-    def transcode_async(self, batches: Sequence[Sequence[bytes]]) -> List[List[Optional[bytes]]]:
-        """Several batches through the asynchronous path, all submitted before the first wait."""
+    def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None) -> List[List[Optional[bytes]]]:
+        """Several batches through the asynchronous path, all submitted before the first wait.
+
+        scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
+        (each a scalar or a per-item sequence)."""
+        for name, v in (("scale", scale), ("max_dim", max_dim)):
+            if v is not None and not isinstance(v, (int, np.integer)) and len(v) != len(batches):
+                raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
         held, tickets = [], []
-        for streams in batches:
+        for bi, streams in enumerate(batches):
             n = len(streams)
+            bsc = scale if scale is None or isinstance(scale, (int, np.integer)) else scale[bi]
+            bmd = max_dim if max_dim is None or isinstance(max_dim, (int, np.integer)) else max_dim[bi]
+            opts = _out_opts(bsc, bmd, n)
             bufs = [_u8(s) for s in streams]
             ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
             sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
@@ -172,7 +239,7 @@ class Engine:
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)(), (ctypes.c_int * n)()
             held.append((bufs, ptrs, sizes, out, offs, lens, status, n))
-            tickets.append(self.submit_raw(ptrs, sizes, n, out, cap, offs, lens, status))
+            tickets.append(self.submit_raw(ptrs, sizes, n, out, cap, offs, lens, status, opts))
         res = []
         for t, (bufs, ptrs, sizes, out, offs, lens, status, n) in zip(tickets, held):
             rc = self.wait(t)
@@ -212,6 +279,20 @@ class Engine:
         if rc < 0:
             raise RuntimeError(f"h2j_engine_decode_batch failed ({rc}): {self.error()}")
         return self._planes(out, info)
+
+    def decode_scaled(self, stream: bytes, scale: int = 0, max_dim: int = 0):
+        """(Y, U, V uint8 numpy, k): the 8-bit planes the JPEG stage reads for this picture at the
+        resolved scale k (include/h2j.h h2j_engine_decode_scaled)."""
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 4)()
+        rc = self._lib.h2j_engine_decode_scaled(self._h, buf, len(stream), int(scale), int(max_dim),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_scaled failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return y, u, v, info[2]
 
     @staticmethod
     def _planes(out, info):

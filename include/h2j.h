@@ -63,6 +63,31 @@ int64_t h2j_engine_submit(h2j_engine *e, int n, const uint8_t *const *data, cons
                           uint8_t *out, size_t out_cap, size_t *out_off, size_t *out_len, int *status);
 int h2j_engine_wait(h2j_engine *e, int64_t ticket);
 
+/* Scaled output (no counterpart in the reference, whose Encoder always encodes the decoded
+ * size): the JPEG of a picture at 1/2, 1/4 or 1/8 of its decoded size, made on the GPU by a box
+ * filter (DESIGN.md "Scaled output" has the exact arithmetic).  For a W x H picture at scale k
+ * the JPEG is W_k x H_k with W_k = 2 ceil(W / 2^(k+1)), H_k = 2 ceil(H / 2^(k+1)); k = 0 is the
+ * unscaled output, byte for byte. */
+typedef struct {
+    int32_t scale_log2; /* 0..3: output at 1/1, 1/2, 1/4, 1/8 */
+    int32_t max_dim;    /* 0: off.  > 0: the smallest k in [scale_log2, 3] with
+                           max(W_k, H_k) <= max_dim; 3 if none fits */
+} h2j_out_opts;
+/* status of an item whose options are invalid (scale_log2 outside 0..3, max_dim < 0); the item
+ * fails alone, with a h2j_engine_frame_error message */
+#define H2J_ERR_OUT_OPTS (-60)
+
+/* h2j_engine_submit / h2j_engine_transcode with per-item output options: opts has n entries
+ * (copied by the call), NULL = all {0, 0}, which is exactly the calls above.  The same stream
+ * may appear several times with different options (the full picture and a thumbnail in one
+ * batch); every item is parsed on its own. */
+int64_t h2j_engine_submit_opts(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                               const h2j_out_opts *opts, uint8_t *out, size_t out_cap, size_t *out_off,
+                               size_t *out_len, int *status);
+int h2j_engine_transcode_opts(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                              const h2j_out_opts *opts, uint8_t *out, size_t out_cap, size_t *out_off,
+                              size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -78,12 +103,18 @@ int h2j_engine_decode_batch(h2j_engine *e, int n, const uint8_t *const *data, co
  * info[0..3] = w, h, qscale, nmcu. */
 int h2j_engine_jpeg_coeffs(h2j_engine *e, const uint8_t *data, size_t size, int16_t *out, size_t cap_elems,
                            int *info);
+/* Inspection of the scaled output: the 8-bit planes K4 reads for this picture -- Y (W_k * H_k)
+ * then U, V ((W_k / 2) * (H_k / 2)), packed -- after K3s (at k = 0: the decoded planes through
+ * the 8-bit conversion K4 applies).  info[0..3] = W_k, H_k, k (resolved), source bit depth. */
+int h2j_engine_decode_scaled(h2j_engine *e, const uint8_t *data, size_t size, int scale_log2, int max_dim,
+                             uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
  * [9] frames  [10] algorithmic bytes of the GPU pixel path  [11] GPU entropy
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
- * picture of the batch: without the wait behind the previous batch). */
+ * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
+ * h2j.py  [22] K3s scaled-output stage (GPU). */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).
@@ -102,6 +133,10 @@ int h2j_engine_chunk_times(h2j_engine *e, double *out, int max_chunks);
  *   lines) is that of IDecoder::H265ToJpeg. */
 int h2j_h265_to_jpeg_mem(const uint8_t *data, size_t size, uint8_t **jpeg, size_t *jpeg_len);
 int h2j_h265_to_jpeg_batch(const char *const *in_paths, const char *const *out_paths, int n, int *ok);
+/* h2j_h265_to_jpeg_mem with scaled output (h2j_out_opts above): concurrent callers with
+ * different scales still share GPU batches. */
+int h2j_h265_to_jpeg_mem_scaled(const uint8_t *data, size_t size, int scale_log2, int max_dim, uint8_t **jpeg,
+                                size_t *jpeg_len);
 void h2j_free(void *p);
 
 /* Library self-description (version, arch, build). */

@@ -73,6 +73,16 @@ constexpr bool h2j_sao_folds_variance(const h2j_frame &f) {
     return f.codec == H2J_CODEC_HEVC && f.pic2 != f.pic && (f.crop_x & 15) == 0 && (f.crop_y & 15) == 0 &&
            (f.out_w & 15) == 0;
 }
+/* Scaled output (DESIGN.md "Scaled output"): luma size of an n-sample dimension at scale k, 2 * ceil(n / 2^(k+1)):
+ * always even, so the JPEG's 4:2:0 chroma is exactly half of it; k = 0 gives n (n even). */
+constexpr int h2j_scaled_dim(int n, int k) { return k ? 2 * ((n + (2 << k) - 1) >> (k + 1)) : n; }
+/* bytes per row of a scaled plane of w samples: whole 16-byte groups (K3s stores dwords, K4c loads 8 bytes) */
+constexpr int h2j_spic_stride(int w) { return (w + 15) & ~15; }
+/* K3s workgroups (256 lanes: 64 dwords of 4 output samples x 4 rows) of one plane and of a picture */
+constexpr int h2j_k3s_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * ((h + 3) >> 2); }
+constexpr int h2j_k3s_tiles(int jpeg_w, int jpeg_h) {
+    return h2j_k3s_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3s_plane_tiles(jpeg_w / 2, jpeg_h / 2);
+}
 #endif
 
 /* JPEG symbol stream (production path): per frame, one tile of H2J_JTILE_BYTES per 256 blocks
@@ -81,6 +91,8 @@ constexpr bool h2j_sao_folds_variance(const h2j_frame &f) {
 #define H2J_JTILE_BYTES (H2J_JSYM_MAX * 256 * 4 + 256 + 512)
 
 #define H2J_SAO_GROUPS 4
+/* K3s launches: sample type (8-bit, high bit depth) x scale (1/2, 1/4, 1/8) */
+#define H2J_SCALE_CLASSES 6
 
 /* One batch of pictures resident in HBM.  All pointers are device pointers. */
 typedef struct {
@@ -126,6 +138,20 @@ typedef struct {
        the H.264 K1 (h2j_k1_recon_h264 on k1map8) on a companion stream */
     int32_t k1hevc_n;
     const uint32_t *k1hevc;
+    /* JPEG source views of the frames: what K4 (variance, FDCT) and K5 read as "the picture".  An
+       unscaled frame is its own view; a scaled frame's view is the 8-bit scaled picture K3s wrote
+       at h2j_scaled.spic (crop 0, out_w x out_h = jpeg_w x jpeg_h, the spic strides and plane offsets, bit
+       depth 8, pic == pic2 so that K4a sums its variances), so the K4 / K5 kernels run the same
+       code for both kinds.  The engine builds them (jpeg_view in engine.cpp); == frames, or NULL,
+       when no picture of the batch is scaled */
+    const h2j_frame *jframes;
+    /* K3s: the scaled pictures (h2j_scaled), grouped by class (3 * (sample type: 0 8-bit, 1 high
+       bit depth) + scale_log2 - 1), one launch per class present; scale_tiles: the most workgroups
+       one picture of the class needs (h2j_k3s_tiles).  K3 SAO may have summed such a picture's
+       unscaled MB variances (h2j_sao_folds_variance knows nothing of scaling); K3s clears the sum and
+       K4a, which sees pic == pic2 in the view, sums those of the scaled picture */
+    const h2j_scaled *scale_map;
+    int32_t scale_first[H2J_SCALE_CLASSES], scale_count[H2J_SCALE_CLASSES], scale_tiles[H2J_SCALE_CLASSES];
 } h2j_gpu_batch;
 
 /* K0 + K1: K0 (all TUs in parallel) availability masks, CTB->TU ranges,
@@ -143,7 +169,11 @@ int h2j_gpu_prof(unsigned long long *out, int n, int reset);
 int h2j_gpu_deblock(const h2j_gpu_batch *b, void *stream);
 /* K3: SAO frame.pic -> frame.pic2 (copies when SAO is off) */
 int h2j_gpu_sao(const h2j_gpu_batch *b, void *stream);
-/* K4: JPEG forward path on frame.pic2 -> frame.jcoef / frame.jstat
+/* K3s: box-filter downscale of the scaled pictures (b->scale_map), cropped frame.pic2 ->
+ * the 8-bit planes at h2j_scaled.spic; no launch when the batch has none */
+int h2j_gpu_scale(const h2j_gpu_batch *b, void *stream);
+/* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
+ * picture) -> frame.jcoef / frame.jstat
  * (variance, rate control, FDCT + quantiser + zigzag, symbol histograms) */
 int h2j_gpu_jpeg(const h2j_gpu_batch *b, void *stream);
 /* K4d alone: Huffman symbol histograms of frame.jcoef -> jstat.hist */

@@ -126,6 +126,20 @@ typedef struct {
     int32_t rext;                   /* HEVC range-extension residual tools K0 applies: H2J_REXT_* */
 } h2j_frame;
 
+/* One scaled picture of a batch (downscaled JPEG output, DESIGN.md "Scaled output"): K3s box-filters
+ * the cropped pic2 of frame `frame` by 2^scale_log2 into an 8-bit planar picture at spic, and K4 / K5
+ * read that picture through the frame's JPEG source view (h2j_gpu_batch.jframes in h2j_gpu.h) instead
+ * of pic2.  Kept beside h2j_frame, not in it: only K3s and the engine need these fields, and every
+ * kernel's per-picture header loads stride over h2j_frame. */
+typedef struct {
+    int32_t frame;                  /* index of the picture in the batch's frames */
+    int32_t scale_log2;             /* 1..3: the JPEG at 1/2, 1/4, 1/8 (0 on the host: not scaled) */
+    int32_t jpeg_w, jpeg_h;         /* JPEG luma size (h2j_scaled_dim of out_w, out_h) */
+    uint64_t spic;                  /* scaled planes (arena offset, bytes) */
+    int32_t spic_stride[3];         /* bytes per row of each scaled plane (multiples of 16) */
+    int32_t spic_off[3];            /* byte offset of each scaled plane inside spic */
+} h2j_scaled;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;
