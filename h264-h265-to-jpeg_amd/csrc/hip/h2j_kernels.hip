@@ -4668,6 +4668,190 @@ __global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __rest
     *reinterpret_cast<uint32_t*>(arena + sc.spic + sc.spic_off[c] + static_cast<uint32_t>(m24(y, sc.spic_stride[c]) + 4 * xd)) = out;
 }
 
+// ---------------------------------------------------------------- K3r: exact-size output
+// Area-average resampling of the final decoded picture (the cropped planes of pic2) to jpeg_w x jpeg_h,
+// any ratio >= 1 per axis, into the 8-bit planar picture at h2j_scaled.spic (as K3s; DESIGN.md
+// "Exact-size output (K3r)").  Each plane on its own grid, pw x ph -> ow x oh; on a common grid of
+// pw ow units source column i covers [i ow, (i + 1) ow) and output column x covers [x pw, (x + 1) pw),
+// the weight wx of i in x is the length of the overlap, rows likewise, and
+//   out = min(255, (2 Sum + D) / (2 D)),  Sum = sum wy wx p,  D = pw ph 2^(bd - 8):
+// one rounding.  The footprints tile the cropped plane: nothing is clamped or replicated.
+// A stream that reads each source row once per strip: a wave is 8 output rows of 64 dwords, a lane makes
+// 4 adjacent output samples per row (one dword store) from the unrounded horizontal sums h_k (< 2^30) of
+// the source rows, adding wy h_k into the 64-bit sum of the output row, or of the two output rows, a
+// source row overlaps.  The rows of a wave are uniform, so the walk down the source rows is scalar
+// control flow; adjacent lanes read adjacent spans.  Two forms of the horizontal sums, both fixed over
+// the rows of a lane:
+//  * 8-bit planes at a horizontal ratio up to 4 (ND = 3 dwords up to 2, 5 up to 4) whose rows start
+//    dword-aligned: the lane's span of at most 4 pw / ow + 2 samples lies in ND aligned dwords; every
+//    byte's weight for every output, low and high byte apart, sits in a register and
+//    h_k = dot4(row, wlo_k) + 256 dot4(row, whi_k)  (v_dot4_u32_u8), ND loads a row;
+//  * else the five column boundaries b = (x0 + k) pw split as b = q ow + rem and
+//    h_k = ow (p[q_k] + ... + p[q_k+1 - 1]) + rem_k+1 p[q_k+1] - rem_k p[q_k], each sample loaded once.
+// The final division has a quotient <= 256: a float estimate of it from the 31 leading bits is within 1,
+// and one exact step corrects it.  NARROW: 2 Sum + D fits 32 bits (257 * 2 D < 2^32: 8-bit pictures up to
+// 3840 x 2160), so the sums and that step are 32-bit; else 64-bit (Sum < 2^59), with the boundary form.
+template <typename Pel, int ND, bool NARROW>
+DEVI void k3r_strip(const Pel* __restrict__ P, uint8_t* __restrict__ O, int ostride, int xd, int y0, int ow, int oh, int pw, int ph,
+                    int cx, int cy, int st, int bd) {
+    constexpr int NW = ND ? ND : 1;
+    uint32_t bnd[5];  // the lane's column boundaries; output columns past the plane (the last dword of a
+                      // row) get empty footprints
+#pragma unroll
+    for (int k = 0; k < 5; k++) bnd[k] = static_cast<uint32_t>(min(4 * xd + k, ow)) * static_cast<uint32_t>(pw);  // <= 2^26
+    const int q0 = static_cast<int>(bnd[0] / static_cast<uint32_t>(ow));
+    // dot form: byte t of the lane's dwords is source column i0 + t (columns outside the plane weigh 0)
+    uint32_t wlo[4][NW], whi[4][NW];
+    int doff[NW];
+    // boundary form; a boundary on the plane's right edge has rem 0: its sample index is clamped, its value unused
+    int q[5], qi[5];
+    uint32_t rem[5];
+    if constexpr (ND > 0) {
+        const int c0 = (cx + q0) & ~3, i0 = c0 - cx;  // row starts are dword-aligned: so is byte c0 of a row
+        const int last = min(static_cast<int>((bnd[4] - (bnd[4] > bnd[0] ? 1u : 0u)) / static_cast<uint32_t>(ow)), pw - 1);
+        const int lastdw = (last - i0) >> 2;  // < ND; the dwords past it are loaded from it again and weigh 0
+#pragma unroll
+        for (int d = 0; d < ND; d++) {
+            doff[d] = c0 + 4 * min(d, lastdw);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint32_t lo = 0, hi = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int i = i0 + 4 * d + b;
+                    const int w = max(0, min((i + 1) * ow, static_cast<int>(bnd[k + 1])) - max(i * ow, static_cast<int>(bnd[k])));
+                    lo |= (static_cast<uint32_t>(w) & 255u) << (8 * b);
+                    hi |= (static_cast<uint32_t>(w) >> 8) << (8 * b);  // w <= ow < 2^16
+                }
+                wlo[k][d] = lo;
+                whi[k][d] = hi;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            q[k] = static_cast<int>(bnd[k] / static_cast<uint32_t>(ow));
+            rem[k] = bnd[k] - static_cast<uint32_t>(q[k]) * static_cast<uint32_t>(ow);
+            qi[k] = min(q[k], pw - 1);
+        }
+    }
+    const unsigned long long D = (static_cast<unsigned long long>(pw) * static_cast<unsigned long long>(ph)) << (bd - 8);
+    const unsigned long long M = 2 * D;  // < 2^36
+    const int sh = NARROW ? 0 : max(0, 42 - static_cast<int>(__builtin_clzll(M)));  // (2 Sum + D) >> sh < 2^31
+    const float rcp = ldexpf(1.0f / static_cast<float>(M), sh);
+    using Acc = typename std::conditional<NARROW, uint32_t, unsigned long long>::type;
+    int jc = -1;  // the source row whose horizontal sums hc holds
+    uint32_t hc[4] = {0, 0, 0, 0};
+    // row boundary y ph = jq oh + jr, stepped from row to row
+    const uint32_t step = static_cast<uint32_t>(ph) / static_cast<uint32_t>(oh), srem = static_cast<uint32_t>(ph) - step * static_cast<uint32_t>(oh);
+    uint32_t jq = static_cast<uint32_t>(y0) * static_cast<uint32_t>(ph) / static_cast<uint32_t>(oh);
+    uint32_t jr = static_cast<uint32_t>(y0) * static_cast<uint32_t>(ph) - jq * static_cast<uint32_t>(oh);
+    for (int r = 0; r < 8 && y0 + r < oh; r++) {
+        const int y = y0 + r;
+        const uint32_t B0 = static_cast<uint32_t>(y) * static_cast<uint32_t>(ph), B1 = B0 + static_cast<uint32_t>(ph);
+        const int jlo = static_cast<int>(jq);
+        jq += step;
+        jr += srem;
+        if (jr >= static_cast<uint32_t>(oh)) {
+            jr -= static_cast<uint32_t>(oh);
+            jq++;
+        }
+        const int jhi = static_cast<int>(jr ? jq : jq - 1);  // the row of unit B1 - 1
+        Acc acc[4] = {0, 0, 0, 0};
+        for (int j = jlo; j <= jhi; j++) {  // jhi <= ph - 1
+            if (j != jc) {
+                jc = j;
+                if constexpr (ND > 0) {
+                    const uint8_t* R = reinterpret_cast<const uint8_t*>(P) + static_cast<uint32_t>(m24(j + cy, st));
+                    uint32_t w[ND];
+#pragma unroll
+                    for (int d = 0; d < ND; d++) w[d] = *reinterpret_cast<const uint32_t*>(R + static_cast<uint32_t>(doff[d]));
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        uint32_t lo = 0, hi = 0;
+#pragma unroll
+                        for (int d = 0; d < ND; d++) {
+                            lo = __builtin_amdgcn_udot4(w[d], wlo[k][d], lo, false);
+                            hi = __builtin_amdgcn_udot4(w[d], whi[k][d], hi, false);
+                        }
+                        hc[k] = lo + (hi << 8);
+                    }
+                } else {
+                    const Pel* R = at32(P, m24(j + cy, st) + cx);
+                    uint32_t e[5];
+#pragma unroll
+                    for (int k = 0; k < 5; k++) e[k] = *at32(R, qi[k]);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        uint32_t seg = q[k + 1] > q[k] ? e[k] : 0u;  // then q[k] is inside the plane
+                        for (int i = q[k] + 1; i < q[k + 1]; i++) seg += *at32(R, i);
+                        hc[k] = static_cast<uint32_t>(ow) * seg + rem[k + 1] * e[k + 1] - rem[k] * e[k];
+                    }
+                }
+            }
+            const uint32_t J0 = static_cast<uint32_t>(j) * static_cast<uint32_t>(oh);
+            const uint32_t wy = min(J0 + static_cast<uint32_t>(oh), B1) - max(J0, B0);
+#pragma unroll
+            for (int k = 0; k < 4; k++) acc[k] += static_cast<Acc>(wy) * hc[k];
+        }
+        uint32_t out = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const Acc N = 2 * acc[k] + static_cast<Acc>(D);
+            uint32_t qq = static_cast<uint32_t>(static_cast<float>(static_cast<uint32_t>(N >> sh)) * rcp);
+            const Acc tq = static_cast<Acc>(qq) * static_cast<Acc>(M);
+            if (tq > N) qq--;
+            else if (N - tq >= static_cast<Acc>(M)) qq++;
+            out |= min(qq, 255u) << (8 * k);
+        }
+        // the row pitch holds whole 16-byte groups: the last dword of a row may run into its padding
+        *reinterpret_cast<uint32_t*>(O + static_cast<uint32_t>(m24(y, ostride) + 4 * xd)) = out;
+    }
+}
+
+template <typename Pel>
+__global__ void __launch_bounds__(256) h2j_k3r_resample(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
+                                                        const h2j_scaled* __restrict__ smap) {
+    const h2j_scaled& sc = smap[blockIdx.y];
+    const h2j_frame& f = frames[sc.frame];
+    if (sc.scale_log2 != H2J_SCALE_RESAMPLE || (f.bit_depth > 8) != (sizeof(Pel) == 2)) return;
+    // as K3s: K4a sums the resized picture's MB variances, not K3 SAO the decoded picture's
+    if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + f.jstat)->var_sum = 0;
+    const int tl = h2j_k3r_plane_tiles(sc.jpeg_w, sc.jpeg_h), tc = h2j_k3r_plane_tiles(sc.jpeg_w >> 1, sc.jpeg_h >> 1);
+    int t = static_cast<int>(blockIdx.x), c = 0;
+    if (t >= tl + 2 * tc) return;
+    if (t >= tl) {
+        t -= tl;
+        c = 1;
+        if (t >= tc) {
+            t -= tc;
+            c = 2;
+        }
+    }
+    const int shc = c ? 1 : 0;
+    const int ow = sc.jpeg_w >> shc, oh = sc.jpeg_h >> shc;  // output plane
+    const int pw = f.out_w >> shc, ph = f.out_h >> shc;      // cropped source plane (pw >= ow, ph >= oh)
+    const int dw = (ow + 3) >> 2, tx = (dw + 63) >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int xd = (t % tx) * 64 + static_cast<int>(threadIdx.x & 63), y0 = (t / tx) * 32 + 8 * wave;
+    if (xd >= dw || y0 >= oh) return;
+    const int cx = f.crop_x >> shc, cy = f.crop_y >> shc, st = f.pic_stride[c];
+    const int bd = c ? f.bit_depth_c : f.bit_depth;
+    const Pel* P = reinterpret_cast<const Pel*>(arena + f.pic2) + f.pic_off[c];
+    uint8_t* const O = arena + sc.spic + sc.spic_off[c];
+    const int os = sc.spic_stride[c];
+    // uniform over the plane: 257 * 2 D < 2^32
+    const bool narrow = ((static_cast<unsigned long long>(pw) * static_cast<unsigned long long>(ph)) << (bd - 8)) < (1ull << 31) / 257;
+    if constexpr (sizeof(Pel) == 1) {
+        // uniform over the plane: its rows start dword-aligned
+        const bool aligned = (((static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c])) | static_cast<uint32_t>(st)) & 3u) == 0;
+        if (aligned && narrow && pw <= 2 * ow) return k3r_strip<Pel, 3, true>(P, O, os, xd, y0, ow, oh, pw, ph, cx, cy, st, bd);
+        if (aligned && narrow && pw <= 4 * ow) return k3r_strip<Pel, 5, true>(P, O, os, xd, y0, ow, oh, pw, ph, cx, cy, st, bd);
+    }
+    if (narrow) return k3r_strip<Pel, 0, true>(P, O, os, xd, y0, ow, oh, pw, ph, cx, cy, st, bd);
+    k3r_strip<Pel, 0, false>(P, O, os, xd, y0, ow, oh, pw, ph, cx, cy, st, bd);
+}
+
 // ---------------------------------------------------------------- K4: JPEG
 template <typename Pel>
 DEVI int jpeg_sample(const h2j_frame& f, const uint8_t* arena, int c, int x, int y) {
@@ -5498,7 +5682,8 @@ int h2j_gpu_sao(const h2j_gpu_batch* b, void* stream) {
 int h2j_gpu_scale(const h2j_gpu_batch* b, void* stream) {
     if (!b || b->nframes <= 0 || !b->scale_map) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // one launch per (sample type, scale) class present: grid = the class's largest picture x its pictures
+    // one launch per class present -- K3s: (sample type, scale), K3r: sample type --: grid = the class's
+    // largest picture x its pictures
     for (int cls = 0; cls < H2J_SCALE_CLASSES; cls++) {
         if (b->scale_count[cls] <= 0 || b->scale_tiles[cls] <= 0) continue;
         const dim3 grid(static_cast<unsigned>(b->scale_tiles[cls]), static_cast<unsigned>(b->scale_count[cls]));
@@ -5509,9 +5694,11 @@ int h2j_gpu_scale(const h2j_gpu_batch* b, void* stream) {
         case 2: hipLaunchKernelGGL((h2j_k3s_downscale<uint8_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
         case 3: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 1>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
         case 4: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 2>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
-        default: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 5: hipLaunchKernelGGL((h2j_k3s_downscale<uint16_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case H2J_K3R_CLASS0: hipLaunchKernelGGL((h2j_k3r_resample<uint8_t>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        default: hipLaunchKernelGGL((h2j_k3r_resample<uint16_t>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
         }
-        if (int rc = check(hipGetLastError(), "h2j_k3s_downscale")) return rc;
+        if (int rc = check(hipGetLastError(), cls < H2J_K3R_CLASS0 ? "h2j_k3s_downscale" : "h2j_k3r_resample")) return rc;
     }
     return 0;
 }

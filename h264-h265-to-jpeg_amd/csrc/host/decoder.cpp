@@ -53,7 +53,8 @@ namespace {
 struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
-    h2j_out_opts opts = {0, 0};  // scaled output (h2j_h265_to_jpeg_mem_scaled); {0, 0}: the decoded size
+    // scaled / exact-size output (h2j_h265_to_jpeg_mem_scaled, _fit); all 0: the decoded size
+    h2j_out_opts2 opts = {0, 0, 0, 0, 0, {0, 0, 0}};
     std::vector<uint8_t> jpeg;
     int status = 0;
     std::string error;
@@ -117,7 +118,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> sizes(n), off(n), len(n);
     std::vector<int> status(n);
-    std::vector<h2j_out_opts> opts(n);
+    std::vector<h2j_out_opts2> opts(n);
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
         opts[i] = batch[i]->opts;
@@ -129,8 +130,8 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = h2j_engine_transcode_opts(e, n, ptrs.data(), sizes.data(), opts.data(), out.data(), cap, off.data(),
-                                      len.data(), status.data());
+        r = h2j_engine_transcode_opts2(e, n, ptrs.data(), sizes.data(), opts.data(), out.data(), cap, off.data(),
+                                       len.data(), status.data());
         bool small = false;
         for (int i = 0; i < n; i++) small = small || status[i] == -50;
         if (!small) break;
@@ -262,8 +263,7 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
 }
 
-extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int scale_log2, int max_dim, uint8_t** jpeg,
-                                           size_t* jpeg_len) {
+static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& opts, uint8_t** jpeg, size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
     *jpeg = nullptr;
     *jpeg_len = 0;
@@ -271,8 +271,7 @@ extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int
     Request req;
     req.data = data;
     req.size = size;
-    req.opts.scale_log2 = scale_log2;
-    req.opts.max_dim = max_dim;
+    req.opts = opts;
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -283,6 +282,16 @@ extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int
     *jpeg = p;
     *jpeg_len = req.jpeg.size();
     return 0;
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int scale_log2, int max_dim, uint8_t** jpeg,
+                                           size_t* jpeg_len) {
+    return to_jpeg_mem(data, size, h2j_out_opts2{scale_log2, max_dim, 0, 0, 0, {0, 0, 0}}, jpeg, jpeg_len);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_fit(const uint8_t* data, size_t size, int fit_w, int fit_h, int flags, uint8_t** jpeg,
+                                        size_t* jpeg_len) {
+    return to_jpeg_mem(data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, jpeg, jpeg_len);
 }
 
 extern "C" void h2j_free(void* p) { free(p); }

@@ -178,31 +178,64 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
 }
 
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
-// max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does)
-bool out_opts_valid(const h2j_out_opts& o) { return o.scale_log2 >= 0 && o.scale_log2 <= 3 && o.max_dim >= 0; }
-int resolve_scale(const h2j_out_opts& o, int w, int h) {
+// max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does).
+// Exact-size output (h2j_out_opts2, the engine's one option type; an h2j_out_opts item has the fit
+// fields 0): the size h2j_fit_size gives.
+h2j_out_opts2 opts2_of(const h2j_out_opts& o) { return h2j_out_opts2{o.scale_log2, o.max_dim, 0, 0, 0, {0, 0, 0}}; }
+bool fit_valid(int fit_w, int fit_h, int flags) {
+    return (fit_w == 0 || (fit_w >= 2 && fit_w <= 65535)) && (fit_h == 0 || (fit_h >= 2 && fit_h <= 65535)) &&
+           (flags & ~H2J_FIT_STRETCH) == 0 && !((flags & H2J_FIT_STRETCH) && fit_w == 0 && fit_h == 0);
+}
+bool out_opts_valid(const h2j_out_opts2& o) {
+    if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
+    if (o.reserved[0] || o.reserved[1] || o.reserved[2] || !fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
+    return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
+}
+int resolve_scale(const h2j_out_opts2& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
     return k;
 }
+// the job's output size from valid options and the parsed size.  A fit that resolves to the picture's
+// own size is the unscaled job; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k: the
+// resampler's arithmetic reduces to K3s's there) is the scaled job of that k; K3r gets the rest
+void resolve_output(const h2j_out_opts2& o, FrameJob& job) {
+    const int w = job.hdr.out_w, h = job.hdr.out_h;
+    job.scale_log2 = resolve_scale(o, w, h);
+    job.fit_w = job.fit_h = 0;
+    int ow = w, oh = h;
+    if ((o.fit_w == 0 && o.fit_h == 0) || h2j_fit_size(w, h, o.fit_w, o.fit_h, o.flags, &ow, &oh) != 0) return;
+    if (ow == w && oh == h) return;
+    for (int k = 1; k <= 3; k++)
+        if ((ow << k) == w && (oh << k) == h) {
+            job.scale_log2 = k;
+            return;
+        }
+    job.scale_log2 = H2J_SCALE_RESAMPLE;
+    job.fit_w = ow;
+    job.fit_h = oh;
+}
 // parse one item of a batch with its output options; invalid options fail the item alone
-int parse_item(const uint8_t* d, size_t n, const h2j_out_opts& o, FrameJob& job) {
+int parse_item(const uint8_t* d, size_t n, const h2j_out_opts2& o, FrameJob& job) {
     if (!out_opts_valid(o)) {
         job.clear();
         job.error = H2J_ERR_OUT_OPTS;
         job.message = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
-                      std::to_string(o.max_dim) + " (>= 0)";
+                      std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " +
+                      std::to_string(o.fit_h) + " (0 or 2..65535, not with scale_log2 / max_dim), flags " +
+                      std::to_string(o.flags) + " (stretch needs a size), reserved " +
+                      ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
         return job.error;
     }
     const int r = parse_any(d, n, job);
-    if (r == 0) job.scale_log2 = resolve_scale(o, job.hdr.out_w, job.hdr.out_h);  // needs the parsed size
+    if (r == 0) resolve_output(o, job);  // needs the parsed size
     return r;
 }
 
 // The JPEG source view of a frame: what K4 (variance, FDCT) and K5 read as "the picture"
 // (include/h2j_gpu.h h2j_gpu_batch.jframes).  An unscaled frame is its own view; a scaled frame's
-// view is the 8-bit picture K3s writes at its h2j_scaled record's spic.
+// view is the 8-bit picture K3s or K3r writes at its h2j_scaled record's spic.
 h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc) {
     h2j_frame v = f;
     if (sc.scale_log2 == 0) return v;
@@ -224,7 +257,7 @@ h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc) {
 struct Slot {
     void* stream = nullptr;
     // 9: after the stats D2H, 10 / 11: around the in-stream payload D2H, 12 / 13: around the wait for
-    // the other slot, 14 / 15: around a second (whole) payload copy, 16: after K3s (scaled output)
+    // the other slot, 14 / 15: around a second (whole) payload copy, 16: after K3s / K3r (scaled output)
     void* ev[17] = {nullptr};
     size_t pay_pre = 0;        // payload bytes already copied in-stream by enqueue() (estimated, <= h_seg's capacity)
     double px = 0;             // output pixels of the chunk (payload estimate)
@@ -265,7 +298,7 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s + K3r
 
 // H.264 pictures with more MB rows than this are reconstructed by several K1 workgroups
 constexpr int kK1BandRows = 68;
@@ -289,7 +322,7 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts> opts;            // per-item output options (empty: all {0, 0})
+    std::vector<h2j_out_opts2> opts;           // per-item output options (empty: all zero)
     std::vector<int> bounds;                   // parse chunks: index ranges
     std::vector<int> chunk_of;
     std::unique_ptr<std::atomic<int>[]> left;  // pictures of each parse chunk still being parsed
@@ -427,12 +460,13 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
         f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
         f.xline = 0;
-        // the JPEG's size: the cropped picture, or its scaled size (K4 / K5 work on that picture)
+        // the JPEG's size: the cropped picture, its scaled size or its fit size (K4 / K5 work on that picture)
         h2j_scaled sc{};
         sc.frame = k;
         sc.scale_log2 = j.scale_log2;
-        sc.jpeg_w = h2j_scaled_dim(f.out_w, sc.scale_log2);
-        sc.jpeg_h = h2j_scaled_dim(f.out_h, sc.scale_log2);
+        const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
+        sc.jpeg_w = resample ? j.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
+        sc.jpeg_h = resample ? j.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
         s.scaled[k] = sc;
         s.frames[k] = f;
         max_w = std::max(max_w, f.width);
@@ -476,7 +510,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
             off = align_up(off + (ysz + 2 * csz) * pel, 256);
         }
     int nscaled = 0;
-    for (int k = 0; k < nf; k++) {  // the 8-bit scaled planes K3s writes and K4 reads (scaled pictures only)
+    for (int k = 0; k < nf; k++) {  // the 8-bit scaled planes K3s / K3r write and K4 reads (scaled pictures only)
         h2j_scaled& sc = s.scaled[k];
         if (sc.scale_log2 == 0) continue;
         nscaled++;
@@ -623,18 +657,21 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
             saomap.push_back(e[i].second);
         }
     }
-    // K3s map: the scaled pictures by class (sample type x scale), one launch per class present,
-    // its grid as wide as the class's largest picture needs
+    // K3s / K3r map: the scaled pictures by class (K3s: sample type x scale, K3r: sample type), one
+    // launch per class present, its grid as wide as the class's largest picture needs
     std::vector<h2j_scaled> scalemap;
     int sc_first[H2J_SCALE_CLASSES] = {}, sc_count[H2J_SCALE_CLASSES] = {}, sc_tiles[H2J_SCALE_CLASSES] = {};
     for (int cls = 0; cls < H2J_SCALE_CLASSES && nscaled; cls++) {
         sc_first[cls] = static_cast<int>(scalemap.size());
         for (int k = 0; k < nf; k++) {
             const h2j_scaled& sc = s.scaled[k];
-            if (sc.scale_log2 == 0 || 3 * (s.frames[k].bit_depth > 8 ? 1 : 0) + sc.scale_log2 - 1 != cls) continue;
+            if (sc.scale_log2 == 0) continue;
+            const int hbd = s.frames[k].bit_depth > 8 ? 1 : 0;
+            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
+            if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
             scalemap.push_back(sc);
             sc_count[cls]++;
-            sc_tiles[cls] = std::max(sc_tiles[cls], h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
+            sc_tiles[cls] = std::max(sc_tiles[cls], resample ? h2j_k3r_tiles(sc.jpeg_w, sc.jpeg_h) : h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
         }
     }
     const size_t o_map = align_up(o_sl + nsl + 16, 256);
@@ -642,7 +679,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     const size_t o_sao = align_up(o_all + k1all.size() * 4 + 16, 256);
     const size_t o_map8 = align_up(o_sao + saomap.size() * 4 + 16, 256);
     const size_t o_hev = align_up(o_map8 + k1map8.size() * 4 + 16, 256);
-    // scaled pictures present: the JPEG source views of all frames and the K3s map follow
+    // scaled pictures present: the JPEG source views of all frames and the K3s / K3r map follow
     const size_t o_jfr = align_up(o_hev + k1hevc.size() * 4 + 16, 256);
     const size_t o_scl = nscaled ? align_up(o_jfr + nf * sizeof(h2j_frame), 256) : o_jfr;
     const size_t in_bytes = nscaled ? align_up(o_scl + scalemap.size() * sizeof(h2j_scaled) + 16, 256) : o_jfr;
@@ -745,7 +782,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     b.jpeg_dense = entropy ? 0 : 1;
     {  // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
         int k4a = 0;
-        // (a scaled picture: always K4a, on the scaled picture; K3s clears what K3 may have summed)
+        // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
         for (int k = 0; k < nf; k++) k4a += (h2j_sao_folds_variance(s.frames[k]) && s.scaled[k].scale_log2 == 0) ? 0 : 1;
         b.k4a_frames = k4a;
     }
@@ -776,7 +813,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     h2j_gpu_event_record(s.ev[3], st);
     if (stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[4], st);
-    if (stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s: no launch without scaled pictures
+    if (stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
     h2j_gpu_event_record(s.ev[16], st);
     if (stages >= 4 && h2j_gpu_jpeg(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[5], st);
@@ -935,8 +972,12 @@ constexpr double kSlotHbmBudget = 64e9;  // at most, per slot (two slots per eng
 constexpr int kMaxGpuChunk = 1024;
 static double hbm_estimate(const FrameJob& j) {
     const double px = static_cast<double>(j.hdr.width) * j.hdr.height;
-    // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample; its JPEG regions shrink by more)
-    return px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + (j.scale_log2 ? 1.5 * px / (1 << 2 * j.scale_log2) : 0.0) + (1 << 20);
+    // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample, a resized picture's 1.5 W_o H_o B; its
+    // JPEG regions shrink by more)
+    const double spic = j.scale_log2 == H2J_SCALE_RESAMPLE ? 1.5 * j.fit_w * j.fit_h
+                        : j.scale_log2                     ? 1.5 * px / (1 << 2 * j.scale_log2)
+                                                           : 0.0;
+    return px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + spic + (1 << 20);
 }
 
 void Engine::start_threads() {
@@ -977,7 +1018,7 @@ void Engine::parse_loop() {
             pool->parallel_for(b->n, [&](int k) {
                 const int i = order[static_cast<size_t>(k)];
                 jobs[i].threads = slice_threads;
-                parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts{0, 0} : b->opts[static_cast<size_t>(i)], jobs[i]);
+                parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts2{} : b->opts[static_cast<size_t>(i)], jobs[i]);
                 if (b->left[b->chunk_of[i]].fetch_sub(1) == 1) {
                     std::lock_guard<std::mutex> g2(amu);
                     acv.notify_all();
@@ -1210,8 +1251,8 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 
 // submit one batch; latency: the synchronous plan (small tail chunks), else the throughput plan
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
-                            const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
-                            int* status, bool latency) {
+                            const h2j_out_opts* opts, const h2j_out_opts2* opts2, uint8_t* out, size_t out_cap,
+                            size_t* out_off, size_t* out_len, int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
     b->n = n;
@@ -1222,7 +1263,9 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     b->out_off = out_off;
     b->out_len = out_len;
     b->status = status;
-    if (opts) b->opts.assign(opts, opts + n);
+    if (opts2) b->opts.assign(opts2, opts2 + n);
+    else if (opts)
+        for (int i = 0; i < n; i++) b->opts.push_back(h2j::opts2_of(opts[i]));
     for (int i = 0; i < n; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
@@ -1251,14 +1294,21 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
 int64_t h2j_engine_submit(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* out,
                           size_t out_cap, size_t* out_off, size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, nullptr, out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, opts, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, opts, nullptr, out, out_cap, out_off, out_len, status, false);
+}
+
+int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
+                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
+                                size_t* out_len, int* status) {
+    if (!w || n < 0) return -1;
+    return submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1283,7 +1333,7 @@ int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
 int h2j_engine_transcode(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* out,
                          size_t out_cap, size_t* out_off, size_t* out_len, int* status) {
     if (!w) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1291,8 +1341,37 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, opts, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, opts, nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
+}
+
+int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
+                               const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
+                               size_t* out_len, int* status) {
+    if (!w || n < 0) return -1;
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh) {
+    if (!ow || !oh || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || !h2j::fit_valid(fit_w, fit_h, flags))
+        return H2J_ERR_OUT_OPTS;
+    const int64_t W = w, H = h;
+    const int64_t bw = fit_w ? std::min<int64_t>(fit_w, W) : W, bh = fit_h ? std::min<int64_t>(fit_h, H) : H;
+    int64_t wo, ho;
+    if (flags & H2J_FIT_STRETCH) {
+        wo = 2 * (bw / 2);
+        ho = 2 * (bh / 2);
+    } else if (bw * H <= bh * W) {  // the width binds
+        wo = 2 * (bw / 2);
+        ho = 2 * std::max<int64_t>(1, (H * wo) / (2 * W));
+    } else {
+        ho = 2 * (bh / 2);
+        wo = 2 * std::max<int64_t>(1, (W * ho) / (2 * H));
+    }
+    *ow = static_cast<int>(wo);
+    *oh = static_cast<int>(ho);
+    return 0;
 }
 
 static int single_job(h2j_engine* w, const uint8_t* data, size_t size) {
@@ -1397,17 +1476,17 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
     return 0;
 }
 
-int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
-                             uint8_t* planes_out, size_t cap, int* info) {
+// the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2& o,
+                              uint8_t* planes_out, size_t cap, int* info) {
     if (!w || !data || !planes_out || !info) return -1;
     Engine& e = w->e;
-    const h2j_out_opts o = {scale_log2, max_dim};
     if (!h2j::out_opts_valid(o)) {
         e.fail("invalid output options");
         return H2J_ERR_OUT_OPTS;
     }
     if (single_job(w, data, size)) return -2;
-    e.jobs[0].scale_log2 = h2j::resolve_scale(o, e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h);
+    h2j::resolve_output(o, e.jobs[0]);
     Slot& s = e.slot[0];
     if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
     // the picture K4 would read: the frame's JPEG source view
@@ -1443,6 +1522,16 @@ int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, in
             }
     }
     return 0;
+}
+
+int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
+                             uint8_t* planes_out, size_t cap, int* info) {
+    return decode_jpeg_source(w, data, size, h2j_out_opts2{scale_log2, max_dim, 0, 0, 0, {0, 0, 0}}, planes_out, cap, info);
+}
+
+int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
+                              uint8_t* planes_out, size_t cap, int* info) {
+    return decode_jpeg_source(w, data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, planes_out, cap, info);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

@@ -29,6 +29,9 @@ struct FrameJob {
     // scaled output: the JPEG at 1/2^scale_log2 of the decoded size (the engine sets it after the
     // parse, from the item's output options and the parsed size)
     int scale_log2 = 0;
+    // exact-size output: scale_log2 == H2J_SCALE_RESAMPLE and the JPEG is fit_w x fit_h (h2j_fit_size of
+    // the item's options and the parsed size; a size K3s makes is given to it as scale_log2 1..3)
+    int fit_w = 0, fit_h = 0;
 
     void clear() {
         hdr = h2j_frame{};
@@ -42,6 +45,7 @@ struct FrameJob {
         reorder_delay = false;
         field_pair = false;
         scale_log2 = 0;
+        fit_w = fit_h = 0;
     }
 };
 

@@ -24,6 +24,13 @@ class OutOpts(ctypes.Structure):
     _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32)]
 
 
+class OutOpts2(ctypes.Structure):
+    """include/h2j.h h2j_out_opts2: per-item scaled or exact-size output."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
 
 
@@ -79,6 +86,24 @@ def load_library() -> ctypes.CDLL:
                                                  u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
         lib.h2j_h265_to_jpeg_mem_scaled.restype = ctypes.c_int
         lib.h2j_h265_to_jpeg_mem_scaled.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u8p), szp]
+    # exact-size output: likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_opts2"):
+        opt2p = ctypes.POINTER(OutOpts2)
+        lib.h2j_engine_transcode_opts2.restype = ctypes.c_int
+        lib.h2j_engine_transcode_opts2.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, opt2p, u8p,
+                                                   ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_opts2.restype = ctypes.c_int64
+        lib.h2j_engine_submit_opts2.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, opt2p, u8p,
+                                                ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_decode_resized.restype = ctypes.c_int
+        lib.h2j_engine_decode_resized.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_fit.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_fit.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(u8p), szp]
+        lib.h2j_fit_size.restype = ctypes.c_int
+        lib.h2j_fit_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -124,12 +149,58 @@ def _per_item(v, n, name):
     return v
 
 
-def _out_opts(scale, max_dim, n):
-    """ctypes h2j_out_opts[n], or None (the unscaled call) when neither keyword is given."""
-    if scale is None and max_dim is None:
-        return None
+def _is_pair(v):
+    """A (w, h) pair of ints (0 or None: no bound on that axis)."""
+    return (isinstance(v, (tuple, list)) and len(v) == 2 and
+            all(x is None or isinstance(x, (int, np.integer)) for x in v))
+
+
+def _per_item_fit(fit, n):
+    """fit -> n (w, h) int pairs: one pair for every item, or a per-item sequence of pairs or None."""
+    if fit is None:
+        return [(0, 0)] * n
+    if not _is_pair(fit):
+        fit = list(fit)
+        if len(fit) != n:
+            raise ValueError(f"fit: {len(fit)} entries for {n} streams")
+        for p in fit:
+            if p is not None and not _is_pair(p):
+                raise ValueError(f"fit: {p!r} is not a (w, h) pair")
+    else:
+        fit = [fit] * n
+    return [(0, 0) if p is None else (int(p[0] or 0), int(p[1] or 0)) for p in fit]
+
+
+def _out_opts(scale, max_dim, n, fit=None, stretch=False):
+    """ctypes h2j_out_opts[n], h2j_out_opts2[n] when fit or stretch is given, or None (the unscaled
+    call) when no keyword is."""
+    if fit is None and (stretch is None or stretch is False):
+        if scale is None and max_dim is None:
+            return None
+        sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
+        return (OutOpts * n)(*[OutOpts(a, b) for a, b in zip(sc, md)])
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
-    return (OutOpts * n)(*[OutOpts(a, b) for a, b in zip(sc, md)])
+    ft = _per_item_fit(fit, n)
+    if isinstance(stretch, (bool, np.bool_)) or stretch is None:
+        stf = [bool(stretch)] * n
+    else:
+        stf = [bool(x) for x in stretch]
+        if len(stf) != n:
+            raise ValueError(f"stretch: {len(stf)} entries for {n} streams")
+    return (OutOpts2 * n)(*[OutOpts2(a, b, w, h, FIT_STRETCH if t else 0)
+                            for a, b, (w, h), t in zip(sc, md, ft, stf)])
+
+
+def fit_size(w: int, h: int, fit, stretch: bool = False):
+    """(W_o, H_o): the output size of a cropped w x h picture for fit=(fit_w, fit_h) (0 or None: no
+    bound on that axis) -- include/h2j.h h2j_fit_size, the one place the size rule lives."""
+    ow, oh = ctypes.c_int(0), ctypes.c_int(0)
+    fw, fh = (0, 0) if fit is None else (int(fit[0] or 0), int(fit[1] or 0))
+    rc = load_library().h2j_fit_size(int(w), int(h), fw, fh, FIT_STRETCH if stretch else 0,
+                                     ctypes.byref(ow), ctypes.byref(oh))
+    if rc != 0:
+        raise ValueError(f"h2j_fit_size({w}, {h}, {fw}, {fh}, stretch={bool(stretch)}) failed ({rc})")
+    return ow.value, oh.value
 
 
 class Engine:
@@ -166,17 +237,23 @@ class Engine:
         self._lib.h2j_engine_host_info(self._h, arr, 4)
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
-    def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None) -> List[Optional[bytes]]:
+    def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
+                  stretch=False) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
         smallest scale from `scale` up whose JPEG is at most max_dim wide and high) are scalars
         or per-item sequences (include/h2j.h h2j_out_opts); the same stream may be listed several
-        times with different scales."""
+        times with different scales.
+
+        fit: exact-size output (h2j_out_opts2), a (w, h) box for every item or a per-item sequence
+        of boxes or None; the JPEG is the largest even size inside the box with the aspect kept
+        (fit_size), never larger than the picture; 0 / None leaves an axis unbounded.  stretch (a
+        bool or a per-item sequence): the box is the output size itself."""
         n = len(streams)
         if n == 0:
             return []
-        opts = _out_opts(scale, max_dim, n)
+        opts = _out_opts(scale, max_dim, n, fit, stretch)
         bufs = [_u8(s) for s in streams]
         ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
@@ -189,6 +266,8 @@ class Engine:
             out = (ctypes.c_uint8 * cap)()
             if opts is None:
                 rc = self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+            elif opts._type_ is OutOpts2:
+                rc = self._lib.h2j_engine_transcode_opts2(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
             else:
                 rc = self._lib.h2j_engine_transcode_opts(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
             if not any(status[i] == -50 for i in range(n)):
@@ -206,9 +285,12 @@ class Engine:
 
     def submit_raw(self, ptrs, sizes, n, out, cap, offs, lens, status, opts=None) -> int:
         """Asynchronous batch (h2j_engine_submit): returns a ticket; the ctypes arrays must stay
-        alive until wait(ticket).  opts: h2j_out_opts[n] (h2j_engine_submit_opts) or None."""
+        alive until wait(ticket).  opts: h2j_out_opts[n] (h2j_engine_submit_opts), h2j_out_opts2[n]
+        (h2j_engine_submit_opts2) or None."""
         if opts is None:
             t = self._lib.h2j_engine_submit(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
+        elif opts._type_ is OutOpts2:
+            t = self._lib.h2j_engine_submit_opts2(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
         else:
             t = self._lib.h2j_engine_submit_opts(self._h, n, ptrs, sizes, opts, out, cap, offs, lens, status)
         if t <= 0:
@@ -218,11 +300,16 @@ class Engine:
     def wait(self, ticket: int) -> int:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
-    def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None) -> List[List[Optional[bytes]]]:
+    def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
+                        stretch=False) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
-        (each a scalar or a per-item sequence)."""
+        (each a scalar or a per-item sequence).  fit / stretch likewise: one (w, h) pair / bool for
+        every picture, or one entry per batch (each what transcode() takes)."""
+        for name, v, one in (("fit", fit, _is_pair(fit)), ("stretch", stretch, isinstance(stretch, (bool, np.bool_)))):
+            if v is not None and not one and len(v) != len(batches):
+                raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
         for name, v in (("scale", scale), ("max_dim", max_dim)):
             if v is not None and not isinstance(v, (int, np.integer)) and len(v) != len(batches):
                 raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
@@ -231,7 +318,9 @@ class Engine:
             n = len(streams)
             bsc = scale if scale is None or isinstance(scale, (int, np.integer)) else scale[bi]
             bmd = max_dim if max_dim is None or isinstance(max_dim, (int, np.integer)) else max_dim[bi]
-            opts = _out_opts(bsc, bmd, n)
+            bft = fit if fit is None or _is_pair(fit) else fit[bi]
+            bst = stretch if stretch is None or isinstance(stretch, (bool, np.bool_)) else stretch[bi]
+            opts = _out_opts(bsc, bmd, n, bft, bst)
             bufs = [_u8(s) for s in streams]
             ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
             sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
@@ -279,6 +368,21 @@ class Engine:
         if rc < 0:
             raise RuntimeError(f"h2j_engine_decode_batch failed ({rc}): {self.error()}")
         return self._planes(out, info)
+
+    def decode_resized(self, stream: bytes, fit, stretch: bool = False):
+        """(Y, U, V uint8 numpy, (W_o, H_o)): the 8-bit planes the JPEG stage reads for this picture
+        at the size fit / stretch give (include/h2j.h h2j_engine_decode_resized)."""
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 4)()
+        fw, fh = (0, 0) if fit is None else (int(fit[0] or 0), int(fit[1] or 0))
+        rc = self._lib.h2j_engine_decode_resized(self._h, buf, len(stream), fw, fh, FIT_STRETCH if stretch else 0,
+                                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_resized failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return y, u, v, (int(info[0]), int(info[1]))
 
     def decode_scaled(self, stream: bytes, scale: int = 0, max_dim: int = 0):
         """(Y, U, V uint8 numpy, k): the 8-bit planes the JPEG stage reads for this picture at the

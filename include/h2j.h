@@ -88,6 +88,41 @@ int h2j_engine_transcode_opts(h2j_engine *e, int n, const uint8_t *const *data, 
                               const h2j_out_opts *opts, uint8_t *out, size_t out_cap, size_t *out_off,
                               size_t *out_len, int *status);
 
+/* Exact-size output: the JPEG of a picture at a size the caller names, made on the GPU by an
+ * area-average resampler (DESIGN.md "Exact-size output (K3r)" has the exact arithmetic).
+ * fit_w x fit_h is a box the output fits inside with the picture's aspect kept, or, with
+ * H2J_FIT_STRETCH, the output size itself; a 0 leaves that axis unbounded.  The output never
+ * upscales and is always even (h2j_fit_size below is the rule).  A box no smaller than the
+ * picture gives the unscaled output, byte for byte; a size that is the picture's at 1/2, 1/4 or
+ * 1/8 gives the bytes of that scale_log2. */
+#define H2J_FIT_STRETCH 1
+typedef struct {
+    int32_t scale_log2, max_dim; /* as h2j_out_opts */
+    int32_t fit_w, fit_h;        /* 0: no bound on that axis; else 2..65535 */
+    int32_t flags;               /* H2J_FIT_STRETCH = 1 */
+    int32_t reserved[3];         /* must be 0 */
+} h2j_out_opts2;
+/* Invalid (the item fails alone with H2J_ERR_OUT_OPTS): what is invalid in h2j_out_opts; fit_w or
+ * fit_h negative, 1 or above 65535; unknown flag bits or non-zero reserved; a fit field together
+ * with scale_log2 != 0 or max_dim != 0; H2J_FIT_STRETCH with both fit fields 0. */
+
+/* The size rule, a pure function (no engine, no GPU): the output size *ow x *oh of a cropped
+ * w x h picture (both even, 2..8192) for fit_w, fit_h, flags as in h2j_out_opts2.  With
+ * bw = fit_w ? min(fit_w, w) : w and bh likewise: fit inside, the width binds when
+ * bw * h <= bh * w: ow = 2 (bw / 2), oh = 2 max(1, (h * ow) / (2 w)); else the height binds,
+ * symmetrically; stretch: ow = 2 (bw / 2), oh = 2 (bh / 2).  All divisions floor.
+ * Returns 0, or H2J_ERR_OUT_OPTS for invalid arguments (ow, oh are not written). */
+int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int *ow, int *oh);
+
+/* h2j_engine_submit_opts / h2j_engine_transcode_opts with h2j_out_opts2; an h2j_out_opts item
+ * is the h2j_out_opts2 item with fit_w = fit_h = flags = 0. */
+int64_t h2j_engine_submit_opts2(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap, size_t *out_off,
+                                size_t *out_len, int *status);
+int h2j_engine_transcode_opts2(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                               const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap, size_t *out_off,
+                               size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -108,13 +143,18 @@ int h2j_engine_jpeg_coeffs(h2j_engine *e, const uint8_t *data, size_t size, int1
  * the 8-bit conversion K4 applies).  info[0..3] = W_k, H_k, k (resolved), source bit depth. */
 int h2j_engine_decode_scaled(h2j_engine *e, const uint8_t *data, size_t size, int scale_log2, int max_dim,
                              uint8_t *planes_out, size_t cap, int *info);
+/* The same for exact-size output: the 8-bit planes K4 reads for this picture at the size
+ * h2j_fit_size gives -- Y (W_o * H_o) then U, V ((W_o / 2) * (H_o / 2)), packed.
+ * info[0..3] = W_o, H_o, mode (0 unscaled, 1..3 K3s at that scale_log2, 4 K3r), source bit depth. */
+int h2j_engine_decode_resized(h2j_engine *e, const uint8_t *data, size_t size, int fit_w, int fit_h, int flags,
+                              uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
  * [9] frames  [10] algorithmic bytes of the GPU pixel path  [11] GPU entropy
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
- * h2j.py  [22] K3s scaled-output stage (GPU). */
+ * h2j.py  [22] K3s / K3r scaled- and exact-size-output stage (GPU). */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).
@@ -137,6 +177,10 @@ int h2j_h265_to_jpeg_batch(const char *const *in_paths, const char *const *out_p
  * different scales still share GPU batches. */
 int h2j_h265_to_jpeg_mem_scaled(const uint8_t *data, size_t size, int scale_log2, int max_dim, uint8_t **jpeg,
                                 size_t *jpeg_len);
+/* h2j_h265_to_jpeg_mem with exact-size output (h2j_out_opts2 above: fit_w, fit_h, flags);
+ * concurrent callers with different sizes still share GPU batches. */
+int h2j_h265_to_jpeg_mem_fit(const uint8_t *data, size_t size, int fit_w, int fit_h, int flags, uint8_t **jpeg,
+                             size_t *jpeg_len);
 void h2j_free(void *p);
 
 /* Library self-description (version, arch, build). */

@@ -83,6 +83,11 @@ constexpr int h2j_k3s_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) 
 constexpr int h2j_k3s_tiles(int jpeg_w, int jpeg_h) {
     return h2j_k3s_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3s_plane_tiles(jpeg_w / 2, jpeg_h / 2);
 }
+/* K3r workgroups (256 lanes: 4 waves, each 64 dwords of 4 output samples x a strip of 8 output rows) */
+constexpr int h2j_k3r_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * ((h + 31) >> 5); }
+constexpr int h2j_k3r_tiles(int jpeg_w, int jpeg_h) {
+    return h2j_k3r_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3r_plane_tiles(jpeg_w / 2, jpeg_h / 2);
+}
 #endif
 
 /* JPEG symbol stream (production path): per frame, one tile of H2J_JTILE_BYTES per 256 blocks
@@ -91,8 +96,10 @@ constexpr int h2j_k3s_tiles(int jpeg_w, int jpeg_h) {
 #define H2J_JTILE_BYTES (H2J_JSYM_MAX * 256 * 4 + 256 + 512)
 
 #define H2J_SAO_GROUPS 4
-/* K3s launches: sample type (8-bit, high bit depth) x scale (1/2, 1/4, 1/8) */
-#define H2J_SCALE_CLASSES 6
+/* K3s launches: sample type (8-bit, high bit depth) x scale (1/2, 1/4, 1/8); then K3r's (exact-size
+ * output): 8-bit, high bit depth */
+#define H2J_SCALE_CLASSES 8
+#define H2J_K3R_CLASS0 6
 
 /* One batch of pictures resident in HBM.  All pointers are device pointers. */
 typedef struct {
@@ -149,7 +156,9 @@ typedef struct {
        bit depth) + scale_log2 - 1), one launch per class present; scale_tiles: the most workgroups
        one picture of the class needs (h2j_k3s_tiles).  K3 SAO may have summed such a picture's
        unscaled MB variances (h2j_sao_folds_variance knows nothing of scaling); K3s clears the sum and
-       K4a, which sees pic == pic2 in the view, sums those of the scaled picture */
+       K4a, which sees pic == pic2 in the view, sums those of the scaled picture.
+       K3r: the exact-size pictures (scale_log2 == H2J_SCALE_RESAMPLE) are the classes H2J_K3R_CLASS0 +
+       sample type of the same map, their scale_tiles from h2j_k3r_tiles; the rest holds for them alike */
     const h2j_scaled *scale_map;
     int32_t scale_first[H2J_SCALE_CLASSES], scale_count[H2J_SCALE_CLASSES], scale_tiles[H2J_SCALE_CLASSES];
 } h2j_gpu_batch;
@@ -170,7 +179,8 @@ int h2j_gpu_deblock(const h2j_gpu_batch *b, void *stream);
 /* K3: SAO frame.pic -> frame.pic2 (copies when SAO is off) */
 int h2j_gpu_sao(const h2j_gpu_batch *b, void *stream);
 /* K3s: box-filter downscale of the scaled pictures (b->scale_map), cropped frame.pic2 ->
- * the 8-bit planes at h2j_scaled.spic; no launch when the batch has none */
+ * the 8-bit planes at h2j_scaled.spic, and K3r: area-average resampling of the exact-size
+ * pictures of the same map; no launch when the batch has none */
 int h2j_gpu_scale(const h2j_gpu_batch *b, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat

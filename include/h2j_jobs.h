@@ -131,10 +131,14 @@ typedef struct {
  * read that picture through the frame's JPEG source view (h2j_gpu_batch.jframes in h2j_gpu.h) instead
  * of pic2.  Kept beside h2j_frame, not in it: only K3s and the engine need these fields, and every
  * kernel's per-picture header loads stride over h2j_frame. */
+/* h2j_scaled.scale_log2 of an exact-size picture (DESIGN.md "Exact-size output"): K3r, the area-average
+ * resampler, makes jpeg_w x jpeg_h from the cropped picture instead of K3s */
+#define H2J_SCALE_RESAMPLE 4
 typedef struct {
     int32_t frame;                  /* index of the picture in the batch's frames */
-    int32_t scale_log2;             /* 1..3: the JPEG at 1/2, 1/4, 1/8 (0 on the host: not scaled) */
-    int32_t jpeg_w, jpeg_h;         /* JPEG luma size (h2j_scaled_dim of out_w, out_h) */
+    int32_t scale_log2;             /* 1..3: the JPEG at 1/2, 1/4, 1/8; H2J_SCALE_RESAMPLE: at jpeg_w x jpeg_h
+                                       (0 on the host: not scaled) */
+    int32_t jpeg_w, jpeg_h;         /* JPEG luma size (h2j_scaled_dim of out_w, out_h; the fit size, K3r) */
     uint64_t spic;                  /* scaled planes (arena offset, bytes) */
     int32_t spic_stride[3];         /* bytes per row of each scaled plane (multiples of 16) */
     int32_t spic_off[3];            /* byte offset of each scaled plane inside spic */
