@@ -4597,7 +4597,7 @@ __global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __rest
     if (sc.scale_log2 != K || (f.bit_depth > 8) != (sizeof(Pel) == 2)) return;
     // K3 SAO may have summed this picture's unscaled MB variances (h2j_sao_folds_variance does not know
     // of scaling): the rate control wants those of the scaled picture, which K4a sums after this kernel
-    if (gp.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + f.jstat)->var_sum = 0;
+    if (gp.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + sc.jstat)->var_sum = 0;
     const int tl = h2j_k3s_plane_tiles(sc.jpeg_w, sc.jpeg_h), tc = h2j_k3s_plane_tiles(sc.jpeg_w >> 1, sc.jpeg_h >> 1);
     int t = gp.x, c = 0;
     if (t >= tl + 2 * tc) return;
@@ -4666,6 +4666,129 @@ __global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __rest
     for (int o = 0; o < 4; o++) out |= min((acc[o] + (1u << (sh - 1))) >> sh, 255u) << (8 * o);
     // the row pitch holds whole 16-byte groups: the last dword of a row may run into its padding
     *reinterpret_cast<uint32_t*>(arena + sc.spic + sc.spic_off[c] + static_cast<uint32_t>(m24(y, sc.spic_stride[c]) + 4 * xd)) = out;
+}
+
+// ---------------------------------------------------------------- K3p: renditions
+// Every K3s level a picture's renditions ask for (two or more of 1/2, 1/4, 1/8) from one read of the
+// cropped planes of pic2 (DESIGN.md "Renditions (K3p)").  K3s's level-k output is the rounded sum of
+// the 2^k x 2^k source samples at coordinates clamped to the plane's last column / row; the window of a
+// level-k output is the union of the windows of the four level-(k - 1) outputs under it, clamped
+// coordinates included, so the unrounded sums nest: a lane keeps the level-1 sums of its window, adds
+// them 2 x 2 into the level-2 sums and those into the level-3 sums, and rounds every level from its own
+// sum -- the bytes K3s writes.  The level sizes 2 ceil(n / 2^(k+1)) do not nest (72 x 40: 36 x 20,
+// 18 x 10, 10 x 6), so the grid is K3s's over the coarsest level KC and every finer level's stores are
+// bounds-checked against its own size (a sum beyond it is of clamped samples only and is not stored).
+// A lane makes 4 adjacent outputs of level KC from 2^KC rows of 4 * 2^KC source samples -- K3s's loads
+// at K = KC -- and stores 2^(KC-k) rows of 2^(KC-k) dwords at level k.  Lanes whose columns are not all
+// inside the plane, and planes with unaligned crops or pitches, sum clamped single samples, as in K3s.
+// The dispatcher's own workgroup order, as K3s at K = 2 and 3 (the same read-once stream).
+template <int R, int C>
+DEVI void k3p_store(const unsigned (&a)[R][C], uint8_t* __restrict__ arena, const h2j_scaled& sl, int c, int xd, int y, int sh) {
+    constexpr int D = C / 4;  // dwords per row of this lane
+    const int shc = c ? 1 : 0, ow = sl.jpeg_w >> shc, oh = sl.jpeg_h >> shc;
+    // a row holds whole 16-byte groups and D dwords are at most one: a group that starts inside the
+    // plane lies inside the row (its tail may run into the row's padding, as K3s's last dword)
+    if (xd * 4 * D >= ow) return;
+    uint8_t* O = arena + sl.spic + sl.spic_off[c];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int yy = y * R + r;
+        if (yy >= oh) break;
+        uint32_t out[D];
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            out[d] = 0;
+#pragma unroll
+            for (int o = 0; o < 4; o++) out[d] |= min((a[r][4 * d + o] + (1u << (sh - 1))) >> sh, 255u) << (8 * o);
+        }
+        uint8_t* p = O + static_cast<uint32_t>(m24(yy, sl.spic_stride[c]) + 4 * D * xd);
+        if constexpr (D == 4) *reinterpret_cast<uint4*>(p) = make_uint4(out[0], out[1], out[2], out[3]);
+        else if constexpr (D == 2) *reinterpret_cast<uint2*>(p) = make_uint2(out[0], out[1]);
+        else *reinterpret_cast<uint32_t*>(p) = out[0];
+    }
+}
+template <int R, int C>
+DEVI void k3p_fold(const unsigned (&a)[2 * R][2 * C], unsigned (&b)[R][C]) {
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int x = 0; x < C; x++) b[r][x] = a[2 * r][2 * x] + a[2 * r][2 * x + 1] + a[2 * r + 1][2 * x] + a[2 * r + 1][2 * x + 1];
+}
+template <typename Pel, int KC>
+__global__ void __launch_bounds__(256) h2j_k3p_pyramid(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
+                                                       const h2j_pyramid* __restrict__ pmap) {
+    constexpr int S = 1 << KC;
+    constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;  // dwords of one source row of a lane (16-byte loads)
+    const h2j_pyramid& py = pmap[blockIdx.y];
+    const h2j_frame& f = frames[py.frame];
+    const h2j_scaled& sk = py.lvl[KC - 1];  // the coarsest level: the grid
+    if (!((py.mask >> KC) & 1) || (py.mask >> (KC + 1)) || (f.bit_depth > 8) != (sizeof(Pel) == 2)) return;
+    // as K3s: K4a sums each level's MB variances; K3 SAO may have summed the decoded picture's into the one
+    // that is the frame's own jstat
+    if (blockIdx.x == 0 && threadIdx.x >= 1 && threadIdx.x <= KC && ((py.mask >> threadIdx.x) & 1))
+        reinterpret_cast<h2j_jstat*>(arena + py.lvl[threadIdx.x - 1].jstat)->var_sum = 0;
+    const int tl = h2j_k3s_plane_tiles(sk.jpeg_w, sk.jpeg_h), tc = h2j_k3s_plane_tiles(sk.jpeg_w >> 1, sk.jpeg_h >> 1);
+    int t = blockIdx.x, c = 0;
+    if (t >= tl + 2 * tc) return;
+    if (t >= tl) {
+        t -= tl;
+        c = 1;
+        if (t >= tc) {
+            t -= tc;
+            c = 2;
+        }
+    }
+    const int shc = c ? 1 : 0;
+    const int ow = sk.jpeg_w >> shc, oh = sk.jpeg_h >> shc;  // level KC's plane
+    const int dw = (ow + 3) >> 2, tx = (dw + 63) >> 6;
+    const int xd = (t % tx) * 64 + static_cast<int>(threadIdx.x & 63), y = (t / tx) * 4 + static_cast<int>(threadIdx.x >> 6);
+    if (xd >= dw || y >= oh) return;
+    const int pw = f.out_w >> shc, ph = f.out_h >> shc;    // cropped source plane
+    const int cx = f.crop_x >> shc, cy = f.crop_y >> shc, st = f.pic_stride[c];
+    const int bd = c ? f.bit_depth_c : f.bit_depth;
+    const Pel* P = reinterpret_cast<const Pel*>(arena + f.pic2) + f.pic_off[c];
+    const int xs = xd * 4 * S, ys = y * S;  // first source column / row of this lane
+    const bool aligned = (((static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) |
+                           (static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel)))) & 15u) == 0;
+    unsigned a1[S / 2][2 * S];  // unrounded level-1 sums: 2 x 2 source samples each
+    if (aligned && xs + 4 * S <= pw) {
+#pragma unroll
+        for (int r = 0; r < S / 2; r++) {
+            uint32_t w0[NW], w1[NW];
+            k3s_load_row<NW>(at32(P, m24(min(ys + 2 * r, ph - 1) + cy, st) + cx + xs), w0);
+            k3s_load_row<NW>(at32(P, m24(min(ys + 2 * r + 1, ph - 1) + cy, st) + cx + xs), w1);
+#pragma unroll
+            for (int q = 0; q < NW; q++) {
+                if constexpr (sizeof(Pel) == 1) {  // a dword: two horizontal pairs
+                    a1[r][2 * q] = __builtin_amdgcn_udot4(w0[q], 0x00000101u, __builtin_amdgcn_udot4(w1[q], 0x00000101u, 0u, false), false);
+                    a1[r][2 * q + 1] = __builtin_amdgcn_udot4(w0[q], 0x01010000u, __builtin_amdgcn_udot4(w1[q], 0x01010000u, 0u, false), false);
+                } else {  // a dword: one horizontal pair; two rows add up packed (2 x (2^14 - 1) < 2^16)
+                    const uint32_t pk = k3s_pk_add_u16(w0[q], w1[q]);
+                    a1[r][q] = (pk & 0xFFFFu) + (pk >> 16);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < S / 2; r++) {
+            const int r0 = m24(min(ys + 2 * r, ph - 1) + cy, st) + cx, r1 = m24(min(ys + 2 * r + 1, ph - 1) + cy, st) + cx;
+#pragma unroll
+            for (int x = 0; x < 2 * S; x++) {
+                const int x0 = min(xs + 2 * x, pw - 1), x1 = min(xs + 2 * x + 1, pw - 1);
+                a1[r][x] = static_cast<unsigned>(*at32(P, r0 + x0)) + static_cast<unsigned>(*at32(P, r0 + x1)) +
+                           static_cast<unsigned>(*at32(P, r1 + x0)) + static_cast<unsigned>(*at32(P, r1 + x1));
+            }
+        }
+    }
+    if (py.mask & 2) k3p_store<S / 2, 2 * S>(a1, arena, py.lvl[0], c, xd, y, 2 + bd - 8);
+    unsigned a2[S / 4][S];
+    k3p_fold<S / 4, S>(a1, a2);
+    if (py.mask & 4) k3p_store<S / 4, S>(a2, arena, py.lvl[1], c, xd, y, 4 + bd - 8);
+    if constexpr (KC == 3) {
+        unsigned a3[1][4];
+        k3p_fold<1, 4>(a2, a3);
+        k3p_store<1, 4>(a3, arena, py.lvl[2], c, xd, y, 6 + bd - 8);
+    }
 }
 
 // ---------------------------------------------------------------- K3r: exact-size output
@@ -4816,7 +4939,7 @@ __global__ void __launch_bounds__(256) h2j_k3r_resample(const h2j_frame* __restr
     const h2j_frame& f = frames[sc.frame];
     if (sc.scale_log2 != H2J_SCALE_RESAMPLE || (f.bit_depth > 8) != (sizeof(Pel) == 2)) return;
     // as K3s: K4a sums the resized picture's MB variances, not K3 SAO the decoded picture's
-    if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + f.jstat)->var_sum = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<h2j_jstat*>(arena + sc.jstat)->var_sum = 0;
     const int tl = h2j_k3r_plane_tiles(sc.jpeg_w, sc.jpeg_h), tc = h2j_k3r_plane_tiles(sc.jpeg_w >> 1, sc.jpeg_h >> 1);
     int t = static_cast<int>(blockIdx.x), c = 0;
     if (t >= tl + 2 * tc) return;
@@ -5680,8 +5803,22 @@ int h2j_gpu_sao(const h2j_gpu_batch* b, void* stream) {
 }
 
 int h2j_gpu_scale(const h2j_gpu_batch* b, void* stream) {
-    if (!b || b->nframes <= 0 || !b->scale_map) return 0;
+    if (!b || b->nframes <= 0 || (!b->scale_map && !b->pyr_map)) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    // K3p: the pictures with several K3s levels, one launch per class present (sample type, coarsest level)
+    for (int cls = 0; cls < H2J_PYR_CLASSES && b->pyr_map; cls++) {
+        if (b->pyr_count[cls] <= 0 || b->pyr_tiles[cls] <= 0) continue;
+        const dim3 grid(static_cast<unsigned>(b->pyr_tiles[cls]), static_cast<unsigned>(b->pyr_count[cls]));
+        const h2j_pyramid* map = b->pyr_map + b->pyr_first[cls];
+        switch (cls) {
+        case 0: hipLaunchKernelGGL((h2j_k3p_pyramid<uint8_t, 2>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 1: hipLaunchKernelGGL((h2j_k3p_pyramid<uint8_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        case 2: hipLaunchKernelGGL((h2j_k3p_pyramid<uint16_t, 2>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        default: hipLaunchKernelGGL((h2j_k3p_pyramid<uint16_t, 3>), grid, dim3(256), 0, s, b->frames, b->arena, map); break;
+        }
+        if (int rc = check(hipGetLastError(), "h2j_k3p_pyramid")) return rc;
+    }
+    if (!b->scale_map) return 0;
     // one launch per class present -- K3s: (sample type, scale), K3r: sample type --: grid = the class's
     // largest picture x its pictures
     for (int cls = 0; cls < H2J_SCALE_CLASSES; cls++) {

@@ -55,6 +55,11 @@ struct Request {
     size_t size = 0;
     // scaled / exact-size output (h2j_h265_to_jpeg_mem_scaled, _fit); all 0: the decoded size
     h2j_out_opts2 opts = {0, 0, 0, 0, 0, {0, 0, 0}};
+    // several renditions of the picture (h2j_h265_to_jpeg_mem_multi): their options, and per rendition
+    // the JPEG and status; empty: the one output `opts` names
+    std::vector<h2j_out_opts2> ropts;
+    std::vector<std::vector<uint8_t>> jpegs;
+    std::vector<int> rstatus;
     std::vector<uint8_t> jpeg;
     int status = 0;
     std::string error;
@@ -111,10 +116,71 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
     return out;
 }
 
+// run one batch in which some request has several renditions: every picture is decoded once
+// (h2j_engine_transcode_multi; a plain request is an item with one rendition)
+void run_batch_multi(h2j_engine* e, std::vector<Request*>& batch) {
+    const int n = static_cast<int>(batch.size());
+    std::vector<const uint8_t*> ptrs(n);
+    std::vector<size_t> sizes(n);
+    std::vector<int32_t> nrend(n);
+    std::vector<int> base(n + 1, 0);
+    std::vector<h2j_out_opts2> opts;
+    size_t cap = 8u << 20;
+    for (int i = 0; i < n; i++) {
+        const Request* q = batch[i];
+        ptrs[i] = q->data;
+        sizes[i] = q->size;
+        nrend[i] = q->ropts.empty() ? 1 : static_cast<int32_t>(q->ropts.size());
+        base[i + 1] = base[i] + nrend[i];
+        if (q->ropts.empty()) opts.push_back(q->opts);
+        else opts.insert(opts.end(), q->ropts.begin(), q->ropts.end());
+        cap += (q->size * 4 + (2u << 20)) * static_cast<size_t>(nrend[i]);
+    }
+    const int total = base[n];
+    std::vector<size_t> off(total), len(total);
+    std::vector<int> status(total);
+    std::vector<uint8_t> out;
+    int r = -1;
+    for (int attempt = 0; attempt < 3; attempt++) {
+        out.resize(cap);
+        r = h2j_engine_transcode_multi(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
+                                       len.data(), status.data());
+        bool small = false;
+        for (int i = 0; i < total; i++) small = small || status[i] == -50;
+        if (!small) break;
+        cap *= 4;
+    }
+    for (int i = 0; i < n; i++) {
+        Request* q = batch[i];
+        const bool multi = !q->ropts.empty();
+        if (multi) {
+            q->jpegs.assign(static_cast<size_t>(nrend[i]), std::vector<uint8_t>());
+            q->rstatus.assign(static_cast<size_t>(nrend[i]), 0);
+        }
+        q->status = 0;
+        for (int k = 0; k < nrend[i]; k++) {
+            const int o = base[i] + k;
+            int st = status[o];
+            if (r != 0 && st == 0) st = r;
+            if (st == 0) {
+                std::vector<uint8_t>& dst = multi ? q->jpegs[k] : q->jpeg;
+                dst.assign(out.begin() + static_cast<long>(off[o]), out.begin() + static_cast<long>(off[o] + len[o]));
+            } else if (q->error.empty()) {
+                const char* m = status[o] != 0 ? h2j_engine_frame_error(e, o) : "";
+                q->error = (m && *m) ? m : h2j_engine_error(e);
+            }
+            if (multi) q->rstatus[k] = st;
+            else q->status = st;
+        }
+    }
+}
+
 // run one batch (caller holds no lock); fills jpeg / status / error of each request
 void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
     if (n == 0) return;
+    for (const Request* q : batch)
+        if (!q->ropts.empty()) return run_batch_multi(e, batch);
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> sizes(n), off(n), len(n);
     std::vector<int> status(n);
@@ -292,6 +358,40 @@ extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int
 extern "C" int h2j_h265_to_jpeg_mem_fit(const uint8_t* data, size_t size, int fit_w, int fit_h, int flags, uint8_t** jpeg,
                                         size_t* jpeg_len) {
     return to_jpeg_mem(data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, jpeg, jpeg_len);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, uint8_t** jpeg,
+                                          size_t* jpeg_len, int* status) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (!jpeg || !jpeg_len || !status || !opts) return -1;
+    for (int r = 0; r < nrend; r++) {
+        jpeg[r] = nullptr;
+        jpeg_len[r] = 0;
+        status[r] = -1;
+    }
+    if (!data || size == 0) return -1;
+    Request req;
+    req.data = data;
+    req.size = size;
+    req.ropts.assign(opts, opts + nrend);
+    transcode_shared(req);
+    if (req.rstatus.size() != static_cast<size_t>(nrend)) {  // the batch did not run (no HIP device)
+        LOG("transcode failed (%d): %s", req.status, req.error.c_str());
+        return req.status ? req.status : -1;
+    }
+    for (int r = 0; r < nrend; r++) {
+        status[r] = req.rstatus[r];
+        if (status[r] != 0) continue;
+        uint8_t* p = static_cast<uint8_t*>(malloc(std::max<size_t>(1, req.jpegs[r].size())));
+        if (!p) {
+            status[r] = -1;
+            continue;
+        }
+        std::memcpy(p, req.jpegs[r].data(), req.jpegs[r].size());
+        jpeg[r] = p;
+        jpeg_len[r] = req.jpegs[r].size();
+    }
+    return 0;
 }
 
 extern "C" void h2j_free(void* p) { free(p); }

@@ -216,28 +216,66 @@ void resolve_output(const h2j_out_opts2& o, FrameJob& job) {
     job.fit_w = ow;
     job.fit_h = oh;
 }
+std::string out_opts_message(const h2j_out_opts2& o) {
+    return "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
+           std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
+           " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
+           " (stretch needs a size), reserved " + ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
+}
 // parse one item of a batch with its output options; invalid options fail the item alone
 int parse_item(const uint8_t* d, size_t n, const h2j_out_opts2& o, FrameJob& job) {
     if (!out_opts_valid(o)) {
         job.clear();
         job.error = H2J_ERR_OUT_OPTS;
-        job.message = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
-                      std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " +
-                      std::to_string(o.fit_h) + " (0 or 2..65535, not with scale_log2 / max_dim), flags " +
-                      std::to_string(o.flags) + " (stretch needs a size), reserved " +
-                      ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
+        job.message = out_opts_message(o);
         return job.error;
     }
     const int r = parse_any(d, n, job);
     if (r == 0) resolve_output(o, job);  // needs the parsed size
     return r;
 }
+// the same for an item with nr renditions (h2j_engine_transcode_multi): one parse; every rendition's
+// output is resolved on its own, and invalid options fail that rendition alone (the item is not parsed
+// when none is valid).  *ran: the entropy decode ran
+int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts2* o, int nr, FrameJob& job, bool* ran) {
+    *ran = false;
+    int valid = 0;
+    for (int r = 0; r < nr; r++) valid += out_opts_valid(o[r]) ? 1 : 0;
+    if (!valid) {
+        job.clear();
+        job.error = H2J_ERR_OUT_OPTS;
+        job.message = out_opts_message(o[0]);
+        return job.error;
+    }
+    *ran = true;
+    const int rc = parse_any(d, n, job);
+    if (rc) return rc;
+    job.outs.resize(static_cast<size_t>(nr));
+    for (int r = 0; r < nr; r++) {
+        FrameJob::Output& out = job.outs[static_cast<size_t>(r)];
+        out = FrameJob::Output();
+        if (!out_opts_valid(o[r])) {
+            out.error = H2J_ERR_OUT_OPTS;
+            continue;
+        }
+        resolve_output(o[r], job);
+        out.scale_log2 = job.scale_log2;
+        out.fit_w = job.fit_w;
+        out.fit_h = job.fit_h;
+    }
+    job.scale_log2 = job.fit_w = job.fit_h = 0;
+    return 0;
+}
 
 // The JPEG source view of a frame: what K4 (variance, FDCT) and K5 read as "the picture"
 // (include/h2j_gpu.h h2j_gpu_batch.jframes).  An unscaled frame is its own view; a scaled frame's
 // view is the 8-bit picture K3s or K3r writes at its h2j_scaled record's spic.
-h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc) {
+// A frame with several renditions has one view per distinct output, each with its own jcoef / tile
+// region and jstat (the first view keeps the frame's own).
+h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc, uint64_t jcoef) {
     h2j_frame v = f;
+    v.jcoef = jcoef;
+    v.jstat = sc.jstat;
     if (sc.scale_log2 == 0) return v;
     v.pic = v.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
     v.crop_x = v.crop_y = 0;
@@ -266,10 +304,21 @@ struct Slot {
     DevBuf d_in, d_arena, d_seg, d_scratch;
     HostBuf h_in, h_js, h_seg;
     std::vector<h2j_frame> frames;
-    std::vector<h2j_scaled> scaled;  // per frame: its JPEG size and, for a scaled picture, its scaled planes
+    // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
+    // is (frame, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
+    // the first view of a frame -- its unscaled rendition if it has one -- keeps the frame's own jcoef
+    // and jstat.  One rendition per item: nv == nf, view k is frame k
+    std::vector<h2j_scaled> scaled;  // per view: its JPEG size and, for a scaled output, its scaled planes
+    std::vector<uint64_t> vjcoef;    // per view: its jcoef / tile region
+    std::vector<int> vfirst;         // per frame: its first view (nf + 1 entries)
+    struct Rend {
+        int out, view;  // index in the batch's output arrays; the view that holds its JPEG
+    };
+    std::vector<Rend> rends;  // the chunk's renditions (those with valid options), frame-major
     std::vector<int> live;  // job index of each frame of the chunk
     std::vector<FrameJob>* jobs = nullptr;  // the job set `live` indexes
-    h2j_gpu_batch batch{};
+    h2j_gpu_batch batch{};   // K0 .. K3, K3s / K3r / K3p: the frames
+    h2j_gpu_batch jbatch{};  // K4, K5: the views (== batch when nv == nf)
     size_t zero_bytes = 0, jcoef_base = 0, jcoef_bytes = 0, jstat_base = 0, jstat_stride = 0;
     int stages = 0;
     bool entropy = false, pending = false;
@@ -298,7 +347,8 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s + K3r
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s + K3r + K3p
+// ST_RENDITIONS: JPEG outputs of the batch (ST_FRAMES: decoded pictures); ST_PARSED: pictures whose entropy decode ran
 
 // H.264 pictures with more MB rows than this are reconstructed by several K1 workgroups
 constexpr int kK1BandRows = 68;
@@ -322,7 +372,10 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts2> opts;           // per-item output options (empty: all zero)
+    std::vector<h2j_out_opts2> opts;           // per-item output options (empty: all zero); multi: per rendition, item-major
+    std::vector<int> rbase;                    // multi (h2j_engine_submit_multi): first rendition of each item, n + 1 entries; else empty
+    int nout = 0;                              // entries of out_off / out_len / status: n, or the renditions of a multi batch
+    std::atomic<int> nparsed{0};               // items whose entropy decode ran
     std::vector<int> bounds;                   // parse chunks: index ranges
     std::vector<int> chunk_of;
     std::unique_ptr<std::atomic<int>[]> left;  // pictures of each parse chunk still being parsed
@@ -435,7 +488,9 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     s.pending = false;
     if (nf == 0) return 0;
     s.frames.resize(nf);
-    s.scaled.resize(nf);
+    s.scaled.clear();
+    s.rends.clear();
+    s.vfirst.assign(static_cast<size_t>(nf) + 1, 0);
     size_t ntu = 0, ncoef = 0, nctb = 0, nslice = 0, nsl = 0, nblk = 0;
     int max_w = 0, max_h = 0, max_mcu = 0, max_ntu = 0, max_ctbs = 0;
     const std::vector<FrameJob>& jobs = *s.jobs;
@@ -461,21 +516,47 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
         f.xline = 0;
         // the JPEG's size: the cropped picture, its scaled size or its fit size (K4 / K5 work on that picture)
-        h2j_scaled sc{};
-        sc.frame = k;
-        sc.scale_log2 = j.scale_log2;
-        const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
-        sc.jpeg_w = resample ? j.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
-        sc.jpeg_h = resample ? j.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
-        s.scaled[k] = sc;
+        // the frame's views: one per distinct output of its renditions, the unscaled one first
+        const size_t v0 = s.scaled.size();
+        s.vfirst[k] = static_cast<int>(v0);
+        FrameJob::Output one;
+        one.scale_log2 = j.scale_log2;
+        one.fit_w = j.fit_w;
+        one.fit_h = j.fit_h;
+        const FrameJob::Output* outs = j.outs.empty() ? &one : j.outs.data();
+        const int nr = j.outs.empty() ? 1 : static_cast<int>(j.outs.size());
+        auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this output, added if new
+            for (size_t v = v0; v < s.scaled.size(); v++) {
+                const h2j_scaled& sv = s.scaled[v];
+                if (sv.scale_log2 == o.scale_log2 && (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
+                    return static_cast<int>(v);
+            }
+            h2j_scaled sc{};
+            sc.frame = k;
+            sc.scale_log2 = o.scale_log2;
+            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
+            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
+            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
+            s.scaled.push_back(sc);
+            const int mcu = ((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4);
+            max_mcu = std::max(max_mcu, mcu);
+            nblk += static_cast<size_t>(mcu) * 6;
+            return static_cast<int>(s.scaled.size()) - 1;
+        };
+        for (int r = 0; r < nr; r++)
+            if (outs[r].error == 0 && outs[r].scale_log2 == 0) {
+                view_of(outs[r]);
+                break;
+            }
+        for (int r = 0; r < nr; r++)
+            if (outs[r].error == 0) s.rends.push_back(Slot::Rend{j.out_base + r, view_of(outs[r])});
         s.frames[k] = f;
         max_w = std::max(max_w, f.width);
         if (f.codec == H2J_CODEC_HEVC) max_ctbs = std::max(max_ctbs, f.ctb_w * f.ctb_h);
         max_h = std::max(max_h, f.height);
-        const int mcu = ((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4);
-        max_mcu = std::max(max_mcu, mcu);
-        nblk += static_cast<size_t>(mcu) * 6;
     }
+    const int nv = static_cast<int>(s.scaled.size());
+    s.vfirst[nf] = nv;
     // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
     size_t off = 0;
     for (int k = 0; k < nf; k++) {
@@ -487,8 +568,9 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     }
     s.jstat_base = off;
     s.jstat_stride = align_up(sizeof(h2j_jstat), 256);
-    for (int k = 0; k < nf; k++) {
-        s.frames[k].jstat = off;
+    for (int v = 0; v < nv; v++) {  // one per view; a frame's own is its first view's
+        s.scaled[v].jstat = off;
+        if (v == s.vfirst[s.scaled[v].frame]) s.frames[s.scaled[v].frame].jstat = off;
         off += s.jstat_stride;
     }
     s.zero_bytes = off;
@@ -510,7 +592,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
             off = align_up(off + (ysz + 2 * csz) * pel, 256);
         }
     int nscaled = 0;
-    for (int k = 0; k < nf; k++) {  // the 8-bit scaled planes K3s / K3r write and K4 reads (scaled pictures only)
+    for (int k = 0; k < nv; k++) {  // the 8-bit scaled planes K3s / K3r / K3p write and K4 reads (scaled views only)
         h2j_scaled& sc = s.scaled[k];
         if (sc.scale_log2 == 0) continue;
         nscaled++;
@@ -525,9 +607,10 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         off = align_up(off + po, 256);
     }
     s.jcoef_base = off;
-    for (int k = 0; k < nf; k++) {  // dense int16 plane (inspection) or the JPEG symbol tiles
-        h2j_frame& f = s.frames[k];
-        f.jcoef = off;
+    s.vjcoef.resize(static_cast<size_t>(nv));
+    for (int k = 0; k < nv; k++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
+        s.vjcoef[k] = off;
+        if (k == s.vfirst[s.scaled[k].frame]) s.frames[s.scaled[k].frame].jcoef = off;
         const size_t blocks = static_cast<size_t>(((s.scaled[k].jpeg_w + 15) >> 4) * ((s.scaled[k].jpeg_h + 15) >> 4)) * 6;
         off = align_up(off + std::max(blocks * 64 * 2, (blocks + 255) / 256 * static_cast<size_t>(H2J_JTILE_BYTES)), 256);
     }
@@ -659,14 +742,42 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     }
     // K3s / K3r map: the scaled pictures by class (K3s: sample type x scale, K3r: sample type), one
     // launch per class present, its grid as wide as the class's largest picture needs
+    // K3p map: a frame with two or more K3s levels among its views gets one h2j_pyramid instead of a K3s
+    // entry per level, by class (sample type, coarsest level)
+    std::vector<int> levels(static_cast<size_t>(nf), 0);  // per frame: mask of its K3s levels
+    int npyr = 0;
+    for (int v = 0; v < nv && nv > nf; v++)
+        if (s.scaled[v].scale_log2 >= 1 && s.scaled[v].scale_log2 <= 3) levels[s.scaled[v].frame] |= 1 << s.scaled[v].scale_log2;
+    for (int k = 0; k < nf; k++) {
+        if (levels[k] & (levels[k] - 1)) npyr++;
+        else levels[k] = 0;  // one level: K3s
+    }
+    std::vector<h2j_pyramid> pyrmap;
+    int py_first[H2J_PYR_CLASSES] = {}, py_count[H2J_PYR_CLASSES] = {}, py_tiles[H2J_PYR_CLASSES] = {};
+    for (int cls = 0; cls < H2J_PYR_CLASSES && npyr; cls++) {
+        py_first[cls] = static_cast<int>(pyrmap.size());
+        for (int k = 0; k < nf; k++) {
+            if (!levels[k]) continue;
+            const int kc = (levels[k] & 8) ? 3 : 2;
+            if (2 * (s.frames[k].bit_depth > 8 ? 1 : 0) + kc - 2 != cls) continue;
+            h2j_pyramid py{};
+            py.frame = k;
+            py.mask = levels[k];
+            for (int v = s.vfirst[k]; v < s.vfirst[k + 1]; v++)
+                if (s.scaled[v].scale_log2 >= 1 && s.scaled[v].scale_log2 <= 3) py.lvl[s.scaled[v].scale_log2 - 1] = s.scaled[v];
+            pyrmap.push_back(py);
+            py_count[cls]++;
+            py_tiles[cls] = std::max(py_tiles[cls], h2j_k3s_tiles(py.lvl[kc - 1].jpeg_w, py.lvl[kc - 1].jpeg_h));
+        }
+    }
     std::vector<h2j_scaled> scalemap;
     int sc_first[H2J_SCALE_CLASSES] = {}, sc_count[H2J_SCALE_CLASSES] = {}, sc_tiles[H2J_SCALE_CLASSES] = {};
     for (int cls = 0; cls < H2J_SCALE_CLASSES && nscaled; cls++) {
         sc_first[cls] = static_cast<int>(scalemap.size());
-        for (int k = 0; k < nf; k++) {
+        for (int k = 0; k < nv; k++) {
             const h2j_scaled& sc = s.scaled[k];
-            if (sc.scale_log2 == 0) continue;
-            const int hbd = s.frames[k].bit_depth > 8 ? 1 : 0;
+            if (sc.scale_log2 == 0 || (levels[sc.frame] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
+            const int hbd = s.frames[sc.frame].bit_depth > 8 ? 1 : 0;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
             if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
             scalemap.push_back(sc);
@@ -681,18 +792,20 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     const size_t o_hev = align_up(o_map8 + k1map8.size() * 4 + 16, 256);
     // scaled pictures present: the JPEG source views of all frames and the K3s / K3r map follow
     const size_t o_jfr = align_up(o_hev + k1hevc.size() * 4 + 16, 256);
-    const size_t o_scl = nscaled ? align_up(o_jfr + nf * sizeof(h2j_frame), 256) : o_jfr;
-    const size_t in_bytes = nscaled ? align_up(o_scl + scalemap.size() * sizeof(h2j_scaled) + 16, 256) : o_jfr;
+    const bool views = nscaled || nv > nf;  // several renditions of a frame: a views array too
+    const size_t o_scl = views ? align_up(o_jfr + nv * sizeof(h2j_frame), 256) : o_jfr;
+    const size_t o_pyr = views ? align_up(o_scl + scalemap.size() * sizeof(h2j_scaled) + 16, 256) : o_jfr;
+    const size_t in_bytes = npyr ? align_up(o_pyr + pyrmap.size() * sizeof(h2j_pyramid) + 16, 256) : o_pyr;
     if (!s.h_in.ensure(in_bytes)) return fail("pinned host allocation failed");
     if (!s.d_in.ensure(in_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
     if (!s.d_arena.ensure(arena_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
     const int tiles = (max_mcu * 6 + 255) / 256;
-    const size_t seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(nf);
+    const size_t seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(nv);
     if (entropy) {
         if (!s.d_seg.ensure(seg_cap)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-        if (!s.d_scratch.ensure(static_cast<size_t>(nf) * tiles * 4 + 256))
+        if (!s.d_scratch.ensure(static_cast<size_t>(nv) * tiles * 4 + 256))
             return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-        if (!s.h_js.ensure(static_cast<size_t>(nf) * s.jstat_stride + 256)) return fail("pinned host allocation failed");
+        if (!s.h_js.ensure(static_cast<size_t>(nv) * s.jstat_stride + 256)) return fail("pinned host allocation failed");
     }
     std::memcpy(s.h_in.p + o_frames, s.frames.data(), nf * sizeof(h2j_frame));
     if (!k1map.empty()) std::memcpy(s.h_in.p + o_map, k1map.data(), k1map.size() * 4);
@@ -700,10 +813,11 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     if (!saomap.empty()) std::memcpy(s.h_in.p + o_sao, saomap.data(), saomap.size() * 4);
     if (!k1map8.empty()) std::memcpy(s.h_in.p + o_map8, k1map8.data(), k1map8.size() * 4);
     if (!k1hevc.empty()) std::memcpy(s.h_in.p + o_hev, k1hevc.data(), k1hevc.size() * 4);
-    if (nscaled) {
+    if (views) {
         h2j_frame* jv = reinterpret_cast<h2j_frame*>(s.h_in.p + o_jfr);
-        for (int k = 0; k < nf; k++) jv[k] = jpeg_view(s.frames[k], s.scaled[k]);
-        std::memcpy(s.h_in.p + o_scl, scalemap.data(), scalemap.size() * sizeof(h2j_scaled));
+        for (int k = 0; k < nv; k++) jv[k] = jpeg_view(s.frames[s.scaled[k].frame], s.scaled[k], s.vjcoef[k]);
+        if (!scalemap.empty()) std::memcpy(s.h_in.p + o_scl, scalemap.data(), scalemap.size() * sizeof(h2j_scaled));
+        if (npyr) std::memcpy(s.h_in.p + o_pyr, pyrmap.data(), pyrmap.size() * sizeof(h2j_pyramid));
     }
     std::vector<size_t> bt(nf), bc(nf), bk(nf), bs(nf), bl(nf);
     {
@@ -768,8 +882,14 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         b.sao_count[g] = sao_count[g];
         b.sao_ctbs[g] = sao_ctbs[g];
     }
-    b.jframes = nscaled ? reinterpret_cast<const h2j_frame*>(din + o_jfr) : b.frames;
-    b.scale_map = nscaled ? reinterpret_cast<const h2j_scaled*>(din + o_scl) : nullptr;
+    b.jframes = views ? reinterpret_cast<const h2j_frame*>(din + o_jfr) : b.frames;
+    b.scale_map = !scalemap.empty() ? reinterpret_cast<const h2j_scaled*>(din + o_scl) : nullptr;
+    b.pyr_map = npyr ? reinterpret_cast<const h2j_pyramid*>(din + o_pyr) : nullptr;
+    for (int c = 0; c < H2J_PYR_CLASSES; c++) {
+        b.pyr_first[c] = py_first[c];
+        b.pyr_count[c] = py_count[c];
+        b.pyr_tiles[c] = py_tiles[c];
+    }
     for (int c = 0; c < H2J_SCALE_CLASSES; c++) {
         b.scale_first[c] = sc_first[c];
         b.scale_count[c] = sc_count[c];
@@ -783,13 +903,21 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     {  // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
         int k4a = 0;
         // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
-        for (int k = 0; k < nf; k++) k4a += (h2j_sao_folds_variance(s.frames[k]) && s.scaled[k].scale_log2 == 0) ? 0 : 1;
+        for (int k = 0; k < nv; k++) k4a += (h2j_sao_folds_variance(s.frames[s.scaled[k].frame]) && s.scaled[k].scale_log2 == 0) ? 0 : 1;
         b.k4a_frames = k4a;
     }
     b.seg = entropy ? static_cast<uint8_t*>(s.d_seg.p) : nullptr;
     b.seg_cap = entropy ? seg_cap : 0;
     b.seg_total = entropy ? static_cast<uint64_t*>(s.d_scratch.p) : nullptr;
     b.tile_bits = entropy ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(s.d_scratch.p) + 256) : nullptr;
+    // K4 / K5 read only the views and the arena: with several renditions of a frame they run on a
+    // descriptor whose frames are the nv views (nv == nf: the one descriptor, as without renditions)
+    h2j_gpu_batch& jb = s.jbatch;
+    jb = b;
+    if (nv > nf) {
+        jb.nframes = nv;
+        jb.frames = jb.jframes = b.jframes;
+    }
     void* st = s.stream;
     int r = 0;
     r |= h2j_gpu_event_record(s.ev[0], st);
@@ -815,14 +943,14 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     h2j_gpu_event_record(s.ev[4], st);
     if (stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
     h2j_gpu_event_record(s.ev[16], st);
-    if (stages >= 4 && h2j_gpu_jpeg(&b, st)) return drain_fail(s, h2j_gpu_last_error());
+    if (stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[5], st);
-    if (entropy && h2j_gpu_entropy(&b, st)) return drain_fail(s, h2j_gpu_last_error());
+    if (entropy && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[6], st);
     if (entropy) {
         r |= h2j_gpu_memcpy_d2h(s.h_js.p, s.d_scratch.p, 8, st);  // seg_total
         r |= h2j_gpu_memcpy_d2h(s.h_js.p + 256, static_cast<uint8_t*>(s.d_arena.p) + s.jstat_base,
-                                static_cast<size_t>(nf) * s.jstat_stride, st);
+                                static_cast<size_t>(nv) * s.jstat_stride, st);
         if (r) return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
     }
     h2j_gpu_event_record(s.ev[9], st);
@@ -842,7 +970,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     }
     s.pay_pre = 0;
     s.px = 0;
-    for (int k = 0; k < nf; k++) s.px += static_cast<double>(s.scaled[k].jpeg_w) * s.scaled[k].jpeg_h;  // JPEG pixels
+    for (int k = 0; k < nv; k++) s.px += static_cast<double>(s.scaled[k].jpeg_w) * s.scaled[k].jpeg_h;  // JPEG pixels
     if (entropy && s.h_seg.cap > 0) {
         // the copy is sized by the engine's payload-per-pixel estimate (1.3x, 4 KB
         // granules), not by the buffer's high-water mark: a small chunk after a 4K one moves its own
@@ -974,11 +1102,24 @@ static double hbm_estimate(const FrameJob& j) {
     const double px = static_cast<double>(j.hdr.width) * j.hdr.height;
     // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample, a resized picture's 1.5 W_o H_o B; its
     // JPEG regions shrink by more)
-    const double spic = j.scale_log2 == H2J_SCALE_RESAMPLE ? 1.5 * j.fit_w * j.fit_h
-                        : j.scale_log2                     ? 1.5 * px / (1 << 2 * j.scale_log2)
-                                                           : 0.0;
-    return px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + spic + (1 << 20);
+    const int k0 = j.outs.empty() ? j.scale_log2 : j.outs[0].scale_log2;  // the first (or only) output
+    const int fw0 = j.outs.empty() ? j.fit_w : j.outs[0].fit_w, fh0 = j.outs.empty() ? j.fit_h : j.outs[0].fit_h;
+    const double spic = k0 == H2J_SCALE_RESAMPLE ? 1.5 * fw0 * fh0 : k0 ? 1.5 * px / (1 << 2 * k0) : 0.0;
+    double est = px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + spic + (1 << 20);
+    // several renditions: each output beyond the first adds its 8-bit planes (1.5 B per output sample), its
+    // jcoef / tile region and its share of the payload pool (272 B per 8x8 block each: 6.4 B per sample),
+    // and its jstat and tile_bits (a few KB)
+    for (size_t r = 1; r < j.outs.size(); r++) {
+        const FrameJob::Output& o = j.outs[r];
+        if (o.error) continue;
+        const double opx = o.scale_log2 == H2J_SCALE_RESAMPLE ? static_cast<double>(o.fit_w) * o.fit_h
+                                                               : static_cast<double>(j.hdr.out_w) * j.hdr.out_h / (1 << 2 * o.scale_log2);
+        est += 14.5 * opx + 8192;
+    }
+    return est;
 }
+// JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
+static int views_estimate(const FrameJob& j) { return std::max<int>(1, static_cast<int>(j.outs.size())); }
 
 void Engine::start_threads() {
     std::lock_guard<std::mutex> g(amu);
@@ -1018,7 +1159,15 @@ void Engine::parse_loop() {
             pool->parallel_for(b->n, [&](int k) {
                 const int i = order[static_cast<size_t>(k)];
                 jobs[i].threads = slice_threads;
-                parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts2{} : b->opts[static_cast<size_t>(i)], jobs[i]);
+                if (b->rbase.empty()) {
+                    parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts2{} : b->opts[static_cast<size_t>(i)], jobs[i]);
+                    if (jobs[i].error != H2J_ERR_OUT_OPTS) b->nparsed.fetch_add(1, std::memory_order_relaxed);
+                } else {
+                    bool ran = false;
+                    parse_item_multi(b->data[i], b->sizes[i], b->opts.data() + b->rbase[i], b->rbase[i + 1] - b->rbase[i], jobs[i], &ran);
+                    if (ran) b->nparsed.fetch_add(1, std::memory_order_relaxed);
+                }
+                jobs[i].out_base = b->rbase.empty() ? i : b->rbase[i];
                 if (b->left[b->chunk_of[i]].fetch_sub(1) == 1) {
                     std::lock_guard<std::mutex> g2(amu);
                     acv.notify_all();
@@ -1051,13 +1200,20 @@ void Engine::drive_loop() {
         stats[ST_PARSE] = b->t_parsed > 0 ? b->t_parsed - b->t0 : 0;
         stats[ST_PARSE_RUN] = b->t_parsed > 0 ? b->t_parsed - b->t_parse0 : 0;
         stats[ST_TOTAL] = now_ms() - b->t0;
+        stats[ST_PARSED] = b->nparsed.load();
         std::memcpy(b->stats, stats, sizeof(stats));
         b->chunk_log = chunk_log;
         b->err = derr;
-        b->msg.assign(static_cast<size_t>(b->n), std::string());
+        b->msg.assign(static_cast<size_t>(b->nout), std::string());
         if (jobs)
-            for (int i = 0; i < b->n; i++)
-                if (b->status[i] != 0 && (*jobs)[i].error != 0) b->msg[i] = (*jobs)[i].message;
+            for (int i = 0; i < b->n; i++) {
+                const int o0 = b->rbase.empty() ? i : b->rbase[i], o1 = b->rbase.empty() ? i + 1 : b->rbase[i + 1];
+                for (int o = o0; o < o1; o++) {
+                    if (b->status[o] == 0) continue;
+                    if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
+                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)]);
+                }
+            }
         if (b->jobset >= 0) jobset_busy[b->jobset] = false;
         b->rc = rc;
         b->done = true;
@@ -1080,49 +1236,59 @@ int Engine::run_batch(Batch& b) {
     auto assemble = [&](Slot& s) -> int {
         if (sync(s)) return -2;
         const double ta = now_ms();
-        const int nf = static_cast<int>(s.live.size());
+        const int nf = static_cast<int>(s.live.size()), nv = static_cast<int>(s.scaled.size());
+        const int nr = static_cast<int>(s.rends.size());
         const uint8_t* js = s.h_js.p + 256;
-        std::vector<size_t> sz(nf);
+        std::vector<size_t> sz(nv);  // per view: its JPEG, encoded once
         auto size_of = [&](int k) {
             const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
             sz[k] = st->seg_off == ~0ull ? 0 : jpeg_container_size(*st, s.h_seg.p + st->seg_off, kLavcIdent);
         };
-        par(nf, size_of);
-        std::vector<size_t> at(nf);
-        for (int k = 0; k < nf; k++) {
-            const int i = s.live[k];
-            const h2j_jstat* stk = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
-            if (stk->dev_error) {  // a device-side failure (e.g. a K1 band hand-off timed out)
+        par(nv, size_of);
+        // every rendition gets its place in the output; renditions of one view (the same resolved output)
+        // hold the same bytes: the first is written, the others copied from it
+        std::vector<size_t> at(nr);
+        std::vector<int> first(nv, -1);  // per view: its first rendition with a place
+        for (int q = 0; q < nr; q++) {
+            const int i = s.rends[q].out, k = s.rends[q].view;
+            // a device-side failure (e.g. a K1 band hand-off timed out) is recorded in the frame's own jstat
+            const h2j_jstat* stf = reinterpret_cast<const h2j_jstat*>(js + s.vfirst[s.scaled[k].frame] * s.jstat_stride);
+            at[q] = ~static_cast<size_t>(0);
+            if (stf->dev_error) {
                 status[i] = -52;
                 rc = -3;
-                at[k] = ~static_cast<size_t>(0);
                 continue;
             }
             if (!sz[k]) {
                 status[i] = -51;  // payload pool overflow
                 rc = -3;
-                at[k] = ~static_cast<size_t>(0);
                 continue;
             }
             if (pos + sz[k] > b.out_cap) {
                 status[i] = -50;
                 rc = -3;
-                at[k] = ~static_cast<size_t>(0);
                 continue;
             }
-            at[k] = pos;
+            at[q] = pos;
+            if (first[k] < 0) first[k] = q;
             b.out_off[i] = pos;
             b.out_len[i] = sz[k];
             pos += sz[k];
         }
         auto write = [&](int k) {
-            if (at[k] == ~static_cast<size_t>(0)) return;
+            if (first[k] < 0) return;
             const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
             const h2j_scaled& sc = s.scaled[k];
-            jpeg_write_container(*st, s.h_seg.p + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[k]);
+            jpeg_write_container(*st, s.h_seg.p + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[first[k]]);
         };
-        par(nf, write);
+        par(nv, write);
+        if (nr > nv)
+            for (int q = 0; q < nr; q++) {
+                const int k = s.rends[q].view;
+                if (at[q] != ~static_cast<size_t>(0) && first[k] != q) std::memcpy(b.out + at[q], b.out + at[first[k]], sz[k]);
+            }
         stats[ST_ASSEMBLE] += now_ms() - ta;
+        stats[ST_RENDITIONS] += nr;
         stats[ST_FRAMES] += nf;
         return 0;
     };
@@ -1140,16 +1306,20 @@ int Engine::run_batch(Batch& b) {
         double total = 0;
         for (int k = i; k < end; k++) total += hbm_estimate(jobs[k]);
         const double budget = slot_hbm_budget;
+        int range_views = 0;
+        for (int k = i; k < end; k++) range_views += views_estimate(jobs[k]);
         const int parts = std::max(static_cast<int>(std::ceil(total / budget)),
-                                   (end - i + kMaxGpuChunk - 1) / kMaxGpuChunk);
+                                   (range_views + kMaxGpuChunk - 1) / kMaxGpuChunk);
         const double share = total / std::max(1, parts);
         while (i < end && !fail) {
             int j = i;
             double est = 0;
+            int nviews = 0;  // renditions count towards the chunk's size; an item's renditions stay together
             while (j < end && j - i < kMaxGpuChunk) {
                 const double cst = hbm_estimate(jobs[j]);
-                if (j > i && (est + cst > budget || est + cst / 2 > share)) break;
+                if (j > i && (est + cst > budget || est + cst / 2 > share || nviews + views_estimate(jobs[j]) > kMaxGpuChunk)) break;
                 est += cst;
+                nviews += views_estimate(jobs[j]);
                 j++;
             }
             Slot& s = slot[sc & 1];
@@ -1170,7 +1340,12 @@ int Engine::run_batch(Batch& b) {
                     jobs[k].error = -3;
                     jobs[k].message = "field picture (PAFF): no frame from one field (H2J_STRICT_REFERENCE)";
                 }
-                status[k] = jobs[k].error;
+                if (b.rbase.empty()) {
+                    status[k] = jobs[k].error;
+                } else {  // a failed item fails every rendition; else each rendition's own options decide
+                    for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++)
+                        status[o] = jobs[k].error ? jobs[k].error : jobs[k].outs[static_cast<size_t>(o - b.rbase[k])].error;
+                }
                 if (jobs[k].error == 0) s.live.push_back(k);
             }
             Slot& prev = slot[(sc + 1) & 1];
@@ -1252,7 +1427,7 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 // submit one batch; latency: the synchronous plan (small tail chunks), else the throughput plan
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                             const h2j_out_opts* opts, const h2j_out_opts2* opts2, uint8_t* out, size_t out_cap,
-                            size_t* out_off, size_t* out_len, int* status, bool latency) {
+                            size_t* out_off, size_t* out_len, int* status, bool latency, const int32_t* nrend = nullptr) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
     b->n = n;
@@ -1263,10 +1438,16 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     b->out_off = out_off;
     b->out_len = out_len;
     b->status = status;
-    if (opts2) b->opts.assign(opts2, opts2 + n);
+    b->nout = n;
+    if (nrend) {  // several renditions per item: opts2 and the output arrays are item-major over all of them
+        b->rbase.assign(static_cast<size_t>(n) + 1, 0);
+        for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + nrend[i];
+        b->nout = b->rbase[n];
+    }
+    if (opts2) b->opts.assign(opts2, opts2 + b->nout);
     else if (opts)
         for (int i = 0; i < n; i++) b->opts.push_back(h2j::opts2_of(opts[i]));
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < b->nout; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
         status[i] = 0;
@@ -1323,7 +1504,7 @@ int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
     const int rc = b->rc;
     std::memcpy(e.last_stats, b->stats, sizeof(b->stats));
     e.last_chunk_log.swap(b->chunk_log);
-    e.last_status.assign(b->status, b->status + b->n);
+    e.last_status.assign(b->status, b->status + b->nout);
     e.last_msg.swap(b->msg);
     if (rc) e.err = b->err;
     e.batches.erase(it);
@@ -1350,6 +1531,31 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
     const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+// nrend[i] in 1..H2J_MAX_RENDITIONS for every item, and options for them
+static bool renditions_valid(int n, const int32_t* nrend, const h2j_out_opts2* opts) {
+    if (n < 0 || (n > 0 && (!nrend || !opts))) return false;
+    for (int i = 0; i < n; i++)
+        if (nrend[i] < 1 || nrend[i] > H2J_MAX_RENDITIONS) return false;
+    return true;
+}
+
+int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    return submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, false, nrend);
+}
+
+int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                               const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                               int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, true, nrend);
     return h2j_engine_wait(w, t);
 }
 
@@ -1477,26 +1683,44 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 }
 
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2& o,
+// (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2* o, int nrend, int pick,
                               uint8_t* planes_out, size_t cap, int* info) {
-    if (!w || !data || !planes_out || !info) return -1;
+    if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
-    if (!h2j::out_opts_valid(o)) {
-        e.fail("invalid output options");
-        return H2J_ERR_OUT_OPTS;
-    }
+    for (int r = 0; r < nrend; r++)
+        if (!h2j::out_opts_valid(o[r])) {
+            e.fail("invalid output options");
+            return H2J_ERR_OUT_OPTS;
+        }
     if (single_job(w, data, size)) return -2;
-    h2j::resolve_output(o, e.jobs[0]);
+    h2j::FrameJob& job = e.jobs[0];
+    std::vector<h2j::FrameJob::Output> outs(static_cast<size_t>(nrend));
+    for (int r = 0; r < nrend; r++) {
+        h2j::resolve_output(o[r], job);
+        outs[r].scale_log2 = job.scale_log2;
+        outs[r].fit_w = job.fit_w;
+        outs[r].fit_h = job.fit_h;
+    }
+    if (nrend > 1) {
+        job.outs = outs;
+        job.scale_log2 = job.fit_w = job.fit_h = 0;
+    }
+    job.out_base = 0;
     Slot& s = e.slot[0];
     if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
-    // the picture K4 would read: the frame's JPEG source view
+    // the picture K4 would read: the JPEG source view of the rendition
     const h2j_frame& f = s.frames[0];
-    const h2j_scaled& sc = s.scaled[0];
-    const h2j_frame v = h2j::jpeg_view(f, sc);
+    const int vi = s.rends[static_cast<size_t>(pick)].view;
+    const h2j_scaled& sc = s.scaled[vi];
+    const h2j_frame v = h2j::jpeg_view(f, sc, s.vjcoef[vi]);
     const int w_ = v.out_w, h_ = v.out_h;
+    int levels = 0;  // K3s levels among the views: two or more are K3p's
+    for (const h2j_scaled& x : s.scaled)
+        if (x.scale_log2 >= 1 && x.scale_log2 <= 3) levels |= 1 << x.scale_log2;
     info[0] = w_;
     info[1] = h_;
-    info[2] = sc.scale_log2;
+    info[2] = (nrend > 1 && sc.scale_log2 >= 1 && sc.scale_log2 <= 3 && (levels & (levels - 1))) ? 5 : sc.scale_log2;
     info[3] = f.bit_depth;
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
@@ -1526,12 +1750,21 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    return decode_jpeg_source(w, data, size, h2j_out_opts2{scale_log2, max_dim, 0, 0, 0, {0, 0, 0}}, planes_out, cap, info);
+    const h2j_out_opts2 o = {scale_log2, max_dim, 0, 0, 0, {0, 0, 0}};
+    return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    return decode_jpeg_source(w, data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, planes_out, cap, info);
+    const h2j_out_opts2 o = {0, 0, fit_w, fit_h, flags, {0, 0, 0}};
+    return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
+}
+
+int h2j_engine_decode_multi(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, int pick,
+                            uint8_t* planes_out, size_t cap, int* info) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (pick < 0 || pick >= nrend) return -1;
+    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

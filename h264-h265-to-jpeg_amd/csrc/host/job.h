@@ -32,6 +32,13 @@ struct FrameJob {
     // exact-size output: scale_log2 == H2J_SCALE_RESAMPLE and the JPEG is fit_w x fit_h (h2j_fit_size of
     // the item's options and the parsed size; a size K3s makes is given to it as scale_log2 1..3)
     int fit_w = 0, fit_h = 0;
+    // several renditions of one picture (h2j_engine_transcode_multi): the resolved output of each, or its
+    // own error (invalid options fail that rendition alone).  Empty: one output, the fields above
+    struct Output {
+        int scale_log2 = 0, fit_w = 0, fit_h = 0, error = 0;
+    };
+    std::vector<Output> outs;
+    int out_base = 0;  // index of the item's first rendition in the batch's output arrays
 
     void clear() {
         hdr = h2j_frame{};
@@ -46,6 +53,7 @@ struct FrameJob {
         field_pair = false;
         scale_log2 = 0;
         fit_w = fit_h = 0;
+        outs.clear();
     }
 };
 

@@ -32,6 +32,8 @@ class OutOpts2(ctypes.Structure):
 
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
+MAX_RENDITIONS = 8  # include/h2j.h H2J_MAX_RENDITIONS: JPEG outputs of one item of a multi call
+ERR_RENDITIONS = -61  # include/h2j.h H2J_ERR_RENDITIONS: a rendition count outside 1..MAX_RENDITIONS
 
 
 def lib_path() -> str:
@@ -104,6 +106,21 @@ def load_library() -> ctypes.CDLL:
         lib.h2j_fit_size.restype = ctypes.c_int
         lib.h2j_fit_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    # renditions (several JPEGs of one decoded picture): likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_multi"):
+        opt2p = ctypes.POINTER(OutOpts2)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt2p, u8p,
+                                                   ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_multi.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi.argtypes = lib.h2j_engine_transcode_multi.argtypes
+        lib.h2j_engine_decode_multi.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt2p, ctypes.c_int,
+                                                u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt2p, ctypes.POINTER(u8p), szp,
+                                                   ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -134,7 +151,7 @@ def _u8(buf: bytes):
 STAT_KEYS = ["parse_ms", "h2d_ms", "recon_ms", "deblock_ms", "sao_ms", "jpeg_ms", "d2h_ms",
              "assemble_ms", "total_ms", "frames", "alg_bytes", "entropy_ms", "prep_ms", "chunks", "pack_ms",
              "parse_run_ms", "d2h_stats_ms", "d2h_payload_ms", "payload_bytes", "host_grow_ms", "h2d_bytes",
-             "payload_copied_bytes", "scale_ms"]
+             "payload_copied_bytes", "scale_ms", "renditions", "parsed"]
 
 
 def _per_item(v, n, name):
@@ -189,6 +206,89 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
             raise ValueError(f"stretch: {len(stf)} entries for {n} streams")
     return (OutOpts2 * n)(*[OutOpts2(a, b, w, h, FIT_STRETCH if t else 0)
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
+
+
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch")
+
+
+def rendition_spec(spec):
+    """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2.
+
+    A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
+    of scale, max_dim, fit, stretch.  Values are not range-checked here: the engine fails a rendition
+    with invalid options alone (ERR_OUT_OPTS)."""
+    if isinstance(spec, (bool, np.bool_)):
+        raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
+    if isinstance(spec, (int, np.integer)):
+        return (int(spec), 0, 0, 0, 0)
+    if _is_pair(spec):
+        return (0, 0, int(spec[0] or 0), int(spec[1] or 0), 0)
+    if isinstance(spec, dict):
+        bad = [k for k in spec if k not in _SPEC_KEYS]
+        if bad:
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch)")
+        fit = spec.get("fit")
+        if fit is not None and not _is_pair(fit):
+            raise ValueError(f"rendition {spec!r}: fit is not a (w, h) pair")
+        fw, fh = (0, 0) if fit is None else (int(fit[0] or 0), int(fit[1] or 0))
+        return (int(spec.get("scale") or 0), int(spec.get("max_dim") or 0), fw, fh,
+                FIT_STRETCH if spec.get("stretch") else 0)
+    raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
+
+
+def _is_spec(v):
+    return (isinstance(v, (int, np.integer, dict)) and not isinstance(v, (bool, np.bool_))) or _is_pair(v)
+
+
+def normalize_renditions(renditions, n: int):
+    """renditions -> n lists of (scale_log2, max_dim, fit_w, fit_h, flags) tuples, one list per item.
+
+    renditions is one list of specs (rendition_spec) used for every item, or a sequence of n such lists,
+    one per item.  A list of two ints is one list of two scales, not a fit: write a fit inside a list of
+    specs as a tuple, (w, h), or as {"fit": (w, h)}.  Every item has 1..MAX_RENDITIONS renditions."""
+    if renditions is None or isinstance(renditions, (int, np.integer, dict, str, bytes)):
+        raise ValueError("renditions: a list of specs, or one such list per item")
+    renditions = list(renditions)
+    # one list for every item: each element is a spec and not itself a list of specs (a tuple pair is a
+    # fit; a list is read as a per-item list)
+    shared = all(_is_spec(r) and not isinstance(r, list) for r in renditions)
+    if shared:
+        per_item = [renditions] * n
+    else:
+        if len(renditions) != n:
+            raise ValueError(f"renditions: {len(renditions)} per-item lists for {n} streams")
+        for r in renditions:
+            if not isinstance(r, (list, tuple)) or _is_spec(r) and not isinstance(r, list):
+                raise ValueError(f"renditions: {r!r} is not a list of specs")
+        per_item = [list(r) for r in renditions]
+    out = []
+    for specs in per_item:
+        if not 1 <= len(specs) <= MAX_RENDITIONS:
+            raise ValueError(f"renditions: {len(specs)} for one item (1..{MAX_RENDITIONS})")
+        out.append([rendition_spec(x) for x in specs])
+    return out
+
+
+def _multi_cap(streams, per_item, floor):
+    """Output bytes to offer first: per rendition what transcode() offers per item, halved per scale
+    level for a plain scale (a JPEG at 1/4 of the samples is well under half the bytes); too little is
+    retried (-50)."""
+    cap = 0
+    for s, specs in zip(streams, per_item):
+        full = max(floor, 4 * len(s))
+        for scale, max_dim, fw, fh, _ in specs:
+            plain_scale = 0 <= scale <= 3 and not (max_dim or fw or fh)
+            cap += (full >> scale) + 65536 if plain_scale else full
+    return cap
+
+
+def _multi_opts(per_item):
+    """(nrend int32[n], h2j_out_opts2[sum], total) of normalize_renditions' result."""
+    n = len(per_item)
+    nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
+    flat = [t for x in per_item for t in x]
+    opts = (OutOpts2 * len(flat))(*[OutOpts2(a, b, w, h, f) for a, b, w, h, f in flat])
+    return nrend, opts, len(flat)
 
 
 def fit_size(w: int, h: int, fit, stretch: bool = False):
@@ -278,6 +378,93 @@ class Engine:
         self.last_status = [int(status[i]) for i in range(n)]  # per-item status of this call
         mv = memoryview(out)
         return [bytes(mv[offs[i]:offs[i] + lens[i]]) if status[i] == 0 else None for i in range(n)]
+
+    def transcode_multi(self, streams: Sequence[bytes], renditions, out_cap: int = 0) -> List[List[Optional[bytes]]]:
+        """Several JPEGs of every picture from one decode: result[i][r] is rendition r of stream i, the
+        bytes transcode() returns for that stream with the same options (None where it failed).
+
+        renditions: one list of specs for every item, or one such list per item (normalize_renditions);
+        a spec is an int (scale), a (w, h) tuple (fit) or a dict with any of scale, max_dim, fit,
+        stretch.  last_status has the result's shape.  out_cap: the output buffer size tried first
+        (0: an estimate); renditions that did not fit (-50) make the call retry with a larger one."""
+        n = len(streams)
+        per_item = normalize_renditions(renditions, n)
+        if n == 0:
+            self.last_status = []
+            return []
+        nrend, opts, total = _multi_opts(per_item)
+        bufs = [_u8(s) for s in streams]
+        ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
+        sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        cap = int(out_cap) or _multi_cap(streams, per_item, 1 << 20)
+        offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
+        for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
+            out = (ctypes.c_uint8 * cap)()
+            rc = self._lib.h2j_engine_transcode_multi(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
+            if not any(status[i] == -50 for i in range(total)):
+                break
+            cap *= 4
+        if rc < 0 and rc != -3:
+            raise RuntimeError(f"h2j_engine_transcode_multi failed ({rc}): {self.error()}")
+        return self._multi_result(per_item, out, offs, lens, status)
+
+    def _multi_result(self, per_item, out, offs, lens, status):
+        mv = memoryview(out)
+        res, st, o = [], [], 0
+        for specs in per_item:
+            res.append([bytes(mv[offs[o + r]:offs[o + r] + lens[o + r]]) if status[o + r] == 0 else None
+                        for r in range(len(specs))])
+            st.append([int(status[o + r]) for r in range(len(specs))])
+            o += len(specs)
+        self.last_status = st
+        return res
+
+    def transcode_multi_async(self, batches: Sequence[Sequence[bytes]], renditions) -> List[List[List[Optional[bytes]]]]:
+        """transcode_multi for several batches through the asynchronous path, all submitted before the
+        first wait; renditions as in transcode_multi, for every batch (per-item lists: one per item of
+        each batch, so the batches then have the same length)."""
+        held, tickets = [], []
+        for streams in batches:
+            n = len(streams)
+            per_item = normalize_renditions(renditions, n)
+            nrend, opts, total = _multi_opts(per_item)
+            bufs = [_u8(s) for s in streams]
+            ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
+            sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+            cap = _multi_cap(streams, per_item, 2 << 20)
+            out = (ctypes.c_uint8 * cap)()
+            offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
+            held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item))
+            t = self._lib.h2j_engine_submit_multi(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
+            if t <= 0:
+                raise RuntimeError(f"h2j_engine_submit_multi failed ({t})")
+            tickets.append(t)
+        res, sts = [], []
+        for t, h in zip(tickets, held):
+            rc = self.wait(t)
+            if rc < 0 and rc != -3:
+                raise RuntimeError(f"h2j_engine_wait failed ({rc}): {self.error()}")
+            res.append(self._multi_result(h[9], h[5], h[6], h[7], h[8]))
+            sts.append(self.last_status)
+        self.last_status = sts
+        return res
+
+    def decode_multi(self, stream: bytes, renditions, pick: int):
+        """(Y, U, V uint8 numpy, (W_o, H_o), mode): the 8-bit planes the JPEG stage reads for rendition
+        `pick` of this picture with all of `renditions` (a list of specs) in flight; mode 0 unscaled,
+        1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi)."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        _, opts, total = _multi_opts([specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 4)()
+        rc = self._lib.h2j_engine_decode_multi(self._h, buf, len(stream), total, opts, int(pick),
+                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return y, u, v, (int(info[0]), int(info[1])), int(info[2])
 
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""

@@ -80,7 +80,8 @@ typedef struct {
 /* h2j_engine_submit / h2j_engine_transcode with per-item output options: opts has n entries
  * (copied by the call), NULL = all {0, 0}, which is exactly the calls above.  The same stream
  * may appear several times with different options (the full picture and a thumbnail in one
- * batch); every item is parsed on its own. */
+ * batch); every item is parsed on its own (h2j_engine_transcode_multi below parses a picture once
+ * for all of its outputs). */
 int64_t h2j_engine_submit_opts(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
                                const h2j_out_opts *opts, uint8_t *out, size_t out_cap, size_t *out_off,
                                size_t *out_len, int *status);
@@ -123,6 +124,26 @@ int h2j_engine_transcode_opts2(h2j_engine *e, int n, const uint8_t *const *data,
                                const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap, size_t *out_off,
                                size_t *out_len, int *status);
 
+/* Renditions: several JPEGs of one picture from one decode -- the full picture and its thumbnails.
+ * Item i has nrend[i] renditions (1..H2J_MAX_RENDITIONS); opts, out_off, out_len and status are
+ * item-major with sum(nrend) entries (frame errors: h2j_engine_frame_error with that index).  The item
+ * is parsed and reconstructed once.  Rendition r of item i is byte for byte what the single-item call
+ * with opts[r] returns.  A parse or decode failure fails every rendition of the item with the item's
+ * status; invalid opts[r] fail that rendition alone with H2J_ERR_OUT_OPTS; -50 (output buffer too
+ * small) is reported per rendition.  Renditions of one item that resolve to the same output are encoded
+ * once and hold identical bytes.  A GPU chunk never separates the renditions of an item.  (DESIGN.md
+ * "Renditions (K3p)": two or more of the scales 1/2, 1/4, 1/8 of one picture come from one read of it.) */
+#define H2J_MAX_RENDITIONS 8
+/* nrend[i] outside 1..H2J_MAX_RENDITIONS (or no nrend / opts): the call fails before anything runs */
+#define H2J_ERR_RENDITIONS (-61)
+int h2j_engine_transcode_multi(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                               const int32_t *nrend, const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap,
+                               size_t *out_off, size_t *out_len, int *status);
+/* the asynchronous form: a ticket (> 0) for h2j_engine_wait, or H2J_ERR_RENDITIONS */
+int64_t h2j_engine_submit_multi(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -148,13 +169,19 @@ int h2j_engine_decode_scaled(h2j_engine *e, const uint8_t *data, size_t size, in
  * info[0..3] = W_o, H_o, mode (0 unscaled, 1..3 K3s at that scale_log2, 4 K3r), source bit depth. */
 int h2j_engine_decode_resized(h2j_engine *e, const uint8_t *data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t *planes_out, size_t cap, int *info);
+/* The same with all nrend renditions of the picture in flight, for rendition `pick`: the planes are what
+ * the kernel that serves that rendition in such a batch wrote.  info as h2j_engine_decode_resized, and
+ * mode 5: a K3s level written by K3p (the picture has two or more levels among its renditions). */
+int h2j_engine_decode_multi(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts2 *opts,
+                            int pick, uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
  * [9] frames  [10] algorithmic bytes of the GPU pixel path  [11] GPU entropy
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
- * h2j.py  [22] K3s / K3r scaled- and exact-size-output stage (GPU). */
+ * h2j.py  [22] K3s / K3r / K3p scaled- and exact-size-output stage (GPU)  [23] renditions: JPEG outputs
+ * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran. */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).
@@ -181,6 +208,12 @@ int h2j_h265_to_jpeg_mem_scaled(const uint8_t *data, size_t size, int scale_log2
  * concurrent callers with different sizes still share GPU batches. */
 int h2j_h265_to_jpeg_mem_fit(const uint8_t *data, size_t size, int fit_w, int fit_h, int flags, uint8_t **jpeg,
                              size_t *jpeg_len);
+/* h2j_h265_to_jpeg_mem with nrend renditions of the picture (h2j_engine_transcode_multi: one decode).  It
+ * goes through the process-wide batching engine, so concurrent callers still share GPU batches.
+ * jpeg[r] is malloc'ed (release with h2j_free), or NULL where status[r] < 0.  Returns 0 if the call
+ * ran (per-rendition results in status), H2J_ERR_RENDITIONS for nrend outside 1..H2J_MAX_RENDITIONS. */
+int h2j_h265_to_jpeg_mem_multi(const uint8_t *data, size_t size, int nrend, const h2j_out_opts2 *opts, uint8_t **jpeg,
+                               size_t *jpeg_len, int *status);
 void h2j_free(void *p);
 
 /* Library self-description (version, arch, build). */

@@ -88,6 +88,8 @@ constexpr int h2j_k3r_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) 
 constexpr int h2j_k3r_tiles(int jpeg_w, int jpeg_h) {
     return h2j_k3r_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3r_plane_tiles(jpeg_w / 2, jpeg_h / 2);
 }
+/* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
+ * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
 
 /* JPEG symbol stream (production path): per frame, one tile of H2J_JTILE_BYTES per 256 blocks
@@ -100,6 +102,8 @@ constexpr int h2j_k3r_tiles(int jpeg_w, int jpeg_h) {
  * output): 8-bit, high bit depth */
 #define H2J_SCALE_CLASSES 8
 #define H2J_K3R_CLASS0 6
+/* K3p launches: sample type (8-bit, high bit depth) x coarsest level (2, 3) */
+#define H2J_PYR_CLASSES 4
 
 /* One batch of pictures resident in HBM.  All pointers are device pointers. */
 typedef struct {
@@ -150,7 +154,9 @@ typedef struct {
        at h2j_scaled.spic (crop 0, out_w x out_h = jpeg_w x jpeg_h, the spic strides and plane offsets, bit
        depth 8, pic == pic2 so that K4a sums its variances), so the K4 / K5 kernels run the same
        code for both kinds.  The engine builds them (jpeg_view in engine.cpp); == frames, or NULL,
-       when no picture of the batch is scaled */
+       when no picture of the batch is scaled.  A picture with several renditions has one view per
+       distinct output (each with its own jcoef and jstat, the first the frame's own); the engine then
+       runs K4 / K5 on a second descriptor whose nframes counts the views and whose frames are the views */
     const h2j_frame *jframes;
     /* K3s: the scaled pictures (h2j_scaled), grouped by class (3 * (sample type: 0 8-bit, 1 high
        bit depth) + scale_log2 - 1), one launch per class present; scale_tiles: the most workgroups
@@ -161,6 +167,12 @@ typedef struct {
        sample type of the same map, their scale_tiles from h2j_k3r_tiles; the rest holds for them alike */
     const h2j_scaled *scale_map;
     int32_t scale_first[H2J_SCALE_CLASSES], scale_count[H2J_SCALE_CLASSES], scale_tiles[H2J_SCALE_CLASSES];
+    /* K3p: the pictures with two or more K3s levels among their renditions (h2j_pyramid; their levels are
+       not in scale_map), grouped by class (2 * sample type + coarsest level - 2), one launch per class
+       present; pyr_tiles: the most workgroups one picture of the class needs (h2j_k3s_tiles of its coarsest
+       level).  NULL: none */
+    const h2j_pyramid *pyr_map;
+    int32_t pyr_first[H2J_PYR_CLASSES], pyr_count[H2J_PYR_CLASSES], pyr_tiles[H2J_PYR_CLASSES];
 } h2j_gpu_batch;
 
 /* K0 + K1: K0 (all TUs in parallel) availability masks, CTB->TU ranges,
@@ -179,8 +191,9 @@ int h2j_gpu_deblock(const h2j_gpu_batch *b, void *stream);
 /* K3: SAO frame.pic -> frame.pic2 (copies when SAO is off) */
 int h2j_gpu_sao(const h2j_gpu_batch *b, void *stream);
 /* K3s: box-filter downscale of the scaled pictures (b->scale_map), cropped frame.pic2 ->
- * the 8-bit planes at h2j_scaled.spic, and K3r: area-average resampling of the exact-size
- * pictures of the same map; no launch when the batch has none */
+ * the 8-bit planes at h2j_scaled.spic, K3r: area-average resampling of the exact-size
+ * pictures of the same map, and K3p: every K3s level of the pictures of b->pyr_map from one read;
+ * no launch when the batch has none */
 int h2j_gpu_scale(const h2j_gpu_batch *b, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat

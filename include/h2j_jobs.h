@@ -142,7 +142,19 @@ typedef struct {
     uint64_t spic;                  /* scaled planes (arena offset, bytes) */
     int32_t spic_stride[3];         /* bytes per row of each scaled plane (multiples of 16) */
     int32_t spic_off[3];            /* byte offset of each scaled plane inside spic */
+    uint64_t jstat;                 /* the h2j_jstat of this output (arena offset): K3s / K3r / K3p clear its var_sum.
+                                       The frame's own jstat when this is the frame's first JPEG output, else one
+                                       of the output's own (several renditions of one picture) */
 } h2j_scaled;
+
+/* One picture with two or more K3s levels among its renditions (DESIGN.md "Renditions (K3p)"): K3p reads
+ * the cropped pic2 of frame `frame` once and writes the 8-bit planes of every level in `mask` (bit k:
+ * scale_log2 k, 1..3) at lvl[k - 1], the h2j_scaled of that rendition. */
+typedef struct {
+    int32_t frame;                  /* index of the picture in the batch's frames */
+    int32_t mask;                   /* levels present: bits 1..3 */
+    h2j_scaled lvl[3];              /* [k - 1]: the level-k output (valid where mask has bit k) */
+} h2j_pyramid;
 
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
