@@ -8,8 +8,19 @@ namespace h2j {
 #ifdef H2J_CABAC_COUNT  // diagnostics (tools/parse_bench): bins decoded by this thread
 extern thread_local unsigned long long g_bins_ctx, g_bins_byp;
 #define H2J_COUNT(v, n) (v += (n))
+// what HEVC residual_coding was fed (parse_bench -b): syntax counts, then the sub-blocks / transform
+// blocks that took each special path of HevcParser::residual()
+struct ResidualStats {
+    unsigned long long tbs, sb_visited, csbf_bins, sb_coded, sig_bins, sig0_bins, gt1_bins, gt2_bins, last_bins,
+        coefs, sb_by_coefs[5] /* 1, 2, 3, 4-7, >= 8 */, rem_coefs, rem_sbs, sign_batch_sbs, sign_single_sbs;
+    unsigned long long one_coef, one_coef_esc, one_coef_esc_price, one_coef_tskip, one_coef_bypass, one_coef_esc_tskip,
+        one_coef_esc_bypass, dc_last_sb, dc_only_tb, sign_pair;
+};
+extern thread_local ResidualStats g_rstat;
+#define H2J_STAT(f, n) (g_rstat.f += (n))
 #else
 #define H2J_COUNT(v, n) ((void)0)
+#define H2J_STAT(f, n) ((void)0)
 #endif
 
 // Tables are internal to the library: hidden, so the -fPIC code reaches them RIP-relative and not

@@ -23,9 +23,6 @@
 #include "job.h"
 
 namespace h2j {
-#ifdef H2J_CORO
-extern thread_local void (*g_h2j_yield)();  // tools/parse_bench/coro.h experiment
-#endif
 namespace {
 
 enum {
@@ -677,6 +674,7 @@ private:
                         int cbf_cr, int cm, int cux, int cuy, int log2cb);
     template <bool RExt>
     void residual(int log2n, int c, int mode, h2j_tu& tu);
+    int remaining_level(int rice);
     void emit_tu(int x, int y, int log2n, int c, int mode, uint8_t flags, bool cbf, int pred_mode_for_scan);
     void split_ctb_records(size_t first);
     std::vector<h2j_tu> chroma_tmp_;
@@ -1068,6 +1066,35 @@ const uint8_t kSigTs[2][16] = {{C_SIG + 42, C_SIG + 42, C_SIG + 42, C_SIG + 42, 
                                {C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43,
                                 C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43, C_SIG + 43}};
 
+// coeff_abs_level_remaining: unary prefix + suffix, usually both inside one 20-bin peek (one
+// division instead of a bin loop with a mispredicted exit).  -1: prefix too long (a broken stream)
+__attribute__((always_inline)) inline int read_remaining(Cabac& cc, int rice) {
+    constexpr int kPeek = 20;
+    const uint32_t q = cc.bypass_peek(kPeek);
+    const uint32_t inv = ~q << (32 - kPeek);
+    int prefix = inv ? __builtin_clz(inv) : kPeek;
+    if (prefix < kPeek) {
+        const int slen = prefix < 3 ? rice : prefix - 3 + rice, total = prefix + 1 + slen;
+        if (total <= kPeek) {
+            const uint32_t top = q >> (kPeek - total);
+            cc.bypass_skip(total, top);
+            const int suf = static_cast<int>(top & ((1u << slen) - 1u));
+            return prefix < 3 ? (prefix << rice) + suf : (((1 << (prefix - 3)) + 2) << rice) + suf;
+        }
+    }
+    prefix = 0;
+    while (prefix < 32 && cc.bypass()) prefix++;
+    if (prefix < 3) return (prefix << rice) + static_cast<int>(cc.bypass_bits(rice));
+    const int pm3 = prefix - 3;
+    if (pm3 + rice > 30) return -1;
+    return (((1 << pm3) + 2) << rice) + static_cast<int>(cc.bypass_bits(pm3 + rice));
+}
+
+// The same on the engine member, out of line: the one-coefficient path of residual() parks its
+// local engine copy in cc_ around this call (rare: 0.1 % of those sub-blocks carry such a level), so
+// the copy's address is never taken and the escape code is not duplicated into the hot loop.
+__attribute__((noinline)) int HevcParser::remaining_level(int rice) { return read_remaining(cc_, rice); }
+
 // RExt = false: H.265 v1 residual coding (the hot path, unchanged).  RExt = true adds the range
 // extensions' residual tools as FFmpeg 4.3 hevc_cabac.c decodes them: transform skip up to
 // log2_max_transform_skip_block_size, transform-skip contexts, sign data hiding off under implicit
@@ -1096,6 +1123,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         shift = log2n - 2;
     }
     const int maxp = (log2n << 1) - 1;
+    H2J_STAT(tbs, 1);
     // unary prefixes; bins k >> shift share a context (the word forwarded in a register, as in
     // the significance loop below)
     auto last_prefix = [&](CabacState* lc) __attribute__((always_inline)) {
@@ -1106,6 +1134,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             const CabacState lw = lc[ci];
             lc[pk] = pw;
             CabacState w = ci == pk ? pw : lw;
+            H2J_STAT(last_bins, 1);
             const int b = cc.decision(w);
             pw = w;
             pk = ci;
@@ -1137,40 +1166,42 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
     // locate last position in scan order
     const int lastSub = g_scan_inv[scanIdx][lsb][((ly >> 2) << lsb) + (lx >> 2)];
     const int lastPos = g_scan_inv[scanIdx][2][((ly & 3) << 2) + (lx & 3)];
-    uint8_t csbf[8][8];
-    std::memset(csbf, 0, sizeof(csbf));
+    // coded_sub_block_flag of sub-block (xs, ys) at bit ys * 8 + xs, in a register: no per-block
+    // clear of a byte map, no byte loads for the neighbours (positions outside the block stay 0)
+    uint64_t csbm = 0;
+    H2J_STAT(dc_only_tb, (lx | ly) == 0);
     int greater1_ctx = 1;
     const bool sdh = p_->sign_hiding != 0;
-    const int sbw = 1 << lsb;
     uint32_t out[32 * 32];
     int nout = 0;
     const uint16_t* const posTab = g_scan_off[scanIdx][lsb];
     const uint8_t(*const sigtab)[2][16] = g_sigctx[c ? 1 : 0][lsb][scanIdx];
     CabacState* const gt1ctx = ctx + C_GT1 + (c ? 16 : 0);
     for (int i = lastSub; i >= 0; i--) {
-#ifdef H2J_CORO_SB
-        if (i < lastSub && g_h2j_yield) g_h2j_yield();
-#endif
         const int xs = sc[lsb][i][0], ys = sc[lsb][i][1];
+        H2J_STAT(sb_visited, 1);
         bool infer_dc = false;
+        // the right / lower neighbours' flags: bits sp + 1 (none in column 7) and sp + 8
+        const int sp = ys * 8 + xs;
+        const unsigned csr = static_cast<unsigned>(((csbm >> 1) & 0x7f7f7f7f7f7f7f7full) >> sp) & 1u;
+        const unsigned csb = static_cast<unsigned>((csbm >> 8) >> sp) & 1u;
+        unsigned coded = 1;
         if (i < lastSub && i > 0) {
-            int csr = (xs + 1 < sbw) ? csbf[xs + 1][ys] : 0;
-            int csb = (ys + 1 < sbw) ? csbf[xs][ys + 1] : 0;
-            csbf[xs][ys] = static_cast<uint8_t>(cc.decision(ctx[C_CSBF + (csr | csb) + (c ? 2 : 0)]));
+            H2J_STAT(csbf_bins, 1);
+            coded = static_cast<unsigned>(cc.decision(ctx[C_CSBF + (csr | csb) + (c ? 2 : 0)]));
             infer_dc = true;
-        } else {
-            csbf[xs][ys] = 1;
         }
+        csbm |= static_cast<uint64_t>(coded) << sp;
+        const int prevCsbf = static_cast<int>(csr | (csb << 1));
         unsigned sigmask = 0;  // bit nn
         int nstart = 15;
         if (i == lastSub) {
             nstart = lastPos - 1;
             sigmask = 1u << lastPos;
+            H2J_STAT(dc_last_sb, lastPos == 0);
         }
-        if (csbf[xs][ys]) {
-            int prevCsbf = 0;
-            if (xs + 1 < sbw) prevCsbf |= csbf[xs + 1][ys];
-            if (ys + 1 < sbw) prevCsbf |= csbf[xs][ys + 1] << 1;
+        // (a last sub-block whose last position is its DC has no significance bin to read)
+        if (coded && nstart >= 0) {
             const uint8_t* sig = ts_ctx ? kSigTs[c ? 1 : 0] : sigtab[prevCsbf][(xs | ys) ? 1 : 0];
             // bins feed the mask arithmetically (no data-dependent branch per bin).  Consecutive
             // positions often share a context: the word of the previous bin's context stays in a
@@ -1179,6 +1210,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             // next bin needs would put store-to-load forwarding on the decision chain
             unsigned got = 0;
             if (nstart > 0) {
+                H2J_STAT(sig_bins, nstart);
                 int pidx = sig[nstart];
                 CabacState pw = ctx[pidx];
                 got = static_cast<unsigned>(cc.decision(pw)) << nstart;
@@ -1194,19 +1226,68 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
                 ctx[pidx] = pw;
             }
             sigmask |= got;
-            infer_dc = infer_dc && got == 0;
-            if (nstart >= 0) {
-                if (!infer_dc) {
-                    if (cc.decision(ctx[sig[0]])) sigmask |= 1u;
-                } else {
-                    sigmask |= 1u;  // nn == 0 inferred
-                }
+            if (infer_dc && got == 0) {
+                sigmask |= 1u;  // nn == 0 inferred
+            } else {
+                H2J_STAT(sig0_bins, 1);
+                if (cc.decision(ctx[sig[0]])) sigmask |= 1u;
             }
         }
         if (!sigmask) continue;
+        H2J_STAT(sb_coded, 1);
         // greater1 / greater2
         int ctxSet = (i == 0 || c > 0) ? 0 : 2;
         if (greater1_ctx == 0) ctxSet++;
+        const int sb_off = ((ys << 2) << log2n) + (xs << 2);
+#ifdef H2J_CABAC_COUNT
+        {
+            const int nc = __builtin_popcount(sigmask);
+            H2J_STAT(coefs, nc);
+            H2J_STAT(sb_by_coefs[nc == 1 ? 0 : nc == 2 ? 1 : nc == 3 ? 2 : nc < 8 ? 3 : 4], 1);
+            H2J_STAT(gt1_bins, nc < 8 ? nc : 8);
+        }
+#endif
+        if ((sigmask & (sigmask - 1)) == 0) {
+            // One coefficient (54 % of the coded sub-blocks of the 149 KB set), as straight-line
+            // code: one greater1 bin on greater1Ctx 1, greater2 if it is set, one sign, and the
+            // remaining level only after greater2 (baseLevel 3).  Sign hiding needs two positions.
+            H2J_STAT(one_coef, 1);
+            H2J_STAT(sign_single_sbs, 1);
+            H2J_STAT(one_coef_tskip, (tu.flags & H2J_TU_TSKIP) != 0);
+            H2J_STAT(one_coef_bypass, cu_bypass_ != 0);
+            const int g1 = cc.decision(gt1ctx[ctxSet * 4 + 1]);
+            greater1_ctx = g1 ^ 1;
+            int lvl = 1 + g1, g2 = 0;
+            if (g1) {
+                H2J_STAT(gt2_bins, 1);
+                g2 = cc.decision(ctx[C_GT2 + ctxSet + (c ? 4 : 0)]);
+                lvl += g2;
+            }
+            const int neg = cc.bypass();
+            if (g2) {
+                H2J_STAT(one_coef_esc, 1);
+                H2J_STAT(one_coef_esc_price, price);
+                H2J_STAT(one_coef_esc_tskip, (tu.flags & H2J_TU_TSKIP) != 0);
+                H2J_STAT(one_coef_esc_bypass, cu_bypass_ != 0);
+                H2J_STAT(rem_coefs, 1);
+                H2J_STAT(rem_sbs, 1);
+                cc_ = cc;
+                const int rem = remaining_level(price ? *stat / 4 : 0);
+                cc = cc_;
+                if (rem < 0) { err_ = -21; return; }
+                lvl += rem;
+                if (price) {  // StatCoeff update from the sub-block's first remaining level
+                    const int ri = *stat / 4;
+                    if (rem >= (3 << ri)) ++*stat;
+                    else if (2 * rem < (1 << ri) && *stat > 0) --*stat;
+                }
+            }
+            int v = neg ? -lvl : lvl;
+            if (v > 32767) v = 32767;
+            if (v < -32768) v = -32768;
+            out[nout++] = (static_cast<uint32_t>(sb_off + posTab[__builtin_ctz(sigmask)]) << 16) | static_cast<uint16_t>(v);
+            continue;
+        }
         greater1_ctx = 1;
         unsigned g1mask = 0;
         int numG1 = 0, lastG1 = -1;
@@ -1244,12 +1325,20 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         if (g1mask) lastG1 = 31 - __builtin_clz(g1mask);
         const bool hidden = !cu_bypass_ && !no_sdh && (lastSig - firstSig > 3);
         int g2 = 0;
-        if (lastG1 != -1) g2 = cc.decision(ctx[C_GT2 + ctxSet + (c ? 4 : 0)]);
+        if (lastG1 != -1) {
+            H2J_STAT(gt2_bins, 1);
+            g2 = cc.decision(ctx[C_GT2 + ctxSet + (c ? 4 : 0)]);
+        }
         const unsigned signed_mask = (sdh && hidden) ? (sigmask & ~(1u << firstSig)) : sigmask;
         // all sign bins at once; bin i (MSB first) belongs to the i-th highest position, so the
-        // output loop below (highest position first) takes them from the top of qs
+        // output loop below (highest position first) takes them from the top of qs.  Up to two
+        // signs (68 % / 18 % of the coded sub-blocks have one / two) are single bypass steps: the
+        // batch read is a 64-bit division.
         const int ns = __builtin_popcount(signed_mask);
-        const uint32_t q = ns > 1 ? cc.bypass_batch(ns) : (ns ? static_cast<uint32_t>(cc.bypass()) : 0u);
+        H2J_STAT(sign_batch_sbs, ns > 1);
+        H2J_STAT(sign_single_sbs, ns <= 1);
+        H2J_STAT(sign_pair, ns == 2);
+        const uint32_t q = ns > 2 ? cc.bypass_batch(ns) : cc.bypass_bits(ns);
         uint32_t qs = ns ? q << (32 - ns) : 0u;
         // positions that carry coeff_abs_level_remaining (baseLevel reached its cap): greater1
         // set (greater2 set for the one position that has it) among the first eight, and every
@@ -1257,6 +1346,8 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         // keeps the per-coefficient "escape or not" branch off the output loop.
         unsigned esc = g1mask | m_uncoded;
         if (lastG1 >= 0 && !g2) esc &= ~(1u << lastG1);
+        H2J_STAT(rem_coefs, __builtin_popcount(esc));
+        H2J_STAT(rem_sbs, esc != 0);
         int remv[16] = {};
         int rice = price ? *stat / 4 : 0;
         bool stat_done = false;
@@ -1264,46 +1355,19 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             const int nn = 31 - __builtin_clz(e);
             e &= ~(1u << nn);
             const int baseL = 1 + ((g1mask >> nn) & 1) + (nn == lastG1 ? g2 : 0);
-            {
-                // coeff_abs_level_remaining: unary prefix + suffix, usually both inside one
-                // 20-bin peek (one division instead of a bin loop with a mispredicted exit)
-                constexpr int kPeek = 20;
-                const uint32_t q = cc.bypass_peek(kPeek);
-                const uint32_t inv = ~q << (32 - kPeek);
-                int prefix = inv ? __builtin_clz(inv) : kPeek;
-                int rem = -1;
-                if (prefix < kPeek) {
-                    const int slen = prefix < 3 ? rice : prefix - 3 + rice, total = prefix + 1 + slen;
-                    if (total <= kPeek) {
-                        const uint32_t top = q >> (kPeek - total);
-                        cc.bypass_skip(total, top);
-                        const int suf = static_cast<int>(top & ((1u << slen) - 1u));
-                        rem = prefix < 3 ? (prefix << rice) + suf : (((1 << (prefix - 3)) + 2) << rice) + suf;
-                    }
-                }
-                if (rem < 0) {
-                    prefix = 0;
-                    while (prefix < 32 && cc.bypass()) prefix++;
-                    if (prefix < 3) rem = (prefix << rice) + static_cast<int>(cc.bypass_bits(rice));
-                    else {
-                        int pm3 = prefix - 3;
-                        if (pm3 + rice > 30) { err_ = -21; cc_ = cc; return; }
-                        rem = (((1 << pm3) + 2) << rice) + static_cast<int>(cc.bypass_bits(pm3 + rice));
-                    }
-                }
-                remv[nn] = rem;
-                if (baseL + rem > 3 * (1 << rice)) rice = price ? rice + 1 : (rice < 4 ? rice + 1 : 4);
-                if (price && !stat_done) {  // StatCoeff update from the sub-block's first remaining level
-                    const int ri = *stat / 4;
-                    if (rem >= (3 << ri)) ++*stat;
-                    else if (2 * rem < (1 << ri) && *stat > 0) --*stat;
-                    stat_done = true;
-                }
+            const int rem = read_remaining(cc, rice);
+            if (rem < 0) { err_ = -21; cc_ = cc; return; }
+            remv[nn] = rem;
+            if (baseL + rem > 3 * (1 << rice)) rice = price ? rice + 1 : (rice < 4 ? rice + 1 : 4);
+            if (price && !stat_done) {  // StatCoeff update from the sub-block's first remaining level
+                const int ri = *stat / 4;
+                if (rem >= (3 << ri)) ++*stat;
+                else if (2 * rem < (1 << ri) && *stat > 0) --*stat;
+                stat_done = true;
             }
         }
         // sign data hiding: the lowest position (processed last) flips when the level sum is odd
         const int flip_last = (sdh && hidden) ? 1 : 0;
-        const int sb_off = ((ys << 2) << log2n) + (xs << 2);
         int sumAbs = 0;
         for (unsigned mm = sigmask; mm;) {
             const int nn = 31 - __builtin_clz(mm);
@@ -1353,9 +1417,6 @@ void HevcParser::emit_tu(int x, int y, int log2n, int c, int mode, uint8_t flags
     tu.ncoef = 0;
     tu.coef = 0;
     if (cbf) {
-#ifdef H2J_CORO
-        if (g_h2j_yield) g_h2j_yield();
-#endif
         if (rext_) residual<true>(log2n, c, mode, tu);
         else residual<false>(log2n, c, mode, tu);
     }

@@ -20,68 +20,70 @@
 #include "sampler.h"
 #endif
 
-#ifdef H2J_CORO
-#include "coro.h"
+#ifdef H2J_CABAC_COUNT
+#ifdef __linux__
+#include <linux/perf_event.h>
+#include <sys/syscall.h>
+#include <unistd.h>
+#include <cerrno>
+#include <cstring>
+#endif
 namespace h2j {
-thread_local void (*g_h2j_yield)() = nullptr;
+thread_local unsigned long long g_bins_ctx = 0, g_bins_byp = 0;
+thread_local ResidualStats g_rstat = {};
 }
 namespace {
-// -c: the stream list parsed by two coroutines on this thread (even / odd entries), switched
-// before every residual block; the other one alone once a coroutine has run out of pictures
-struct CoPair {
-    h2j_coro::Co co[2], main;
-    int cur = 0;
-    const std::vector<std::vector<uint8_t>>* streams;
-    int reps;
-    double best[2];
-};
-thread_local CoPair* g_pair = nullptr;
-void co_yield() {
-    CoPair& p = *g_pair;
-    const int o = p.cur ^ 1;
-    if (p.co[o].done) return;
-    const int me = p.cur;
-    p.cur = o;
-    h2j_ctx_swap(&p.co[me].sp, p.co[o].sp);
+// -b: a hardware counter of this thread (user mode), or -1 where the kernel does not allow one
+int perf_open(unsigned long long config) {
+#ifdef __linux__
+    perf_event_attr pe;
+    std::memset(&pe, 0, sizeof(pe));
+    pe.type = PERF_TYPE_HARDWARE;
+    pe.size = sizeof(pe);
+    pe.config = config;
+    pe.exclude_kernel = 1;
+    pe.exclude_hv = 1;
+    return static_cast<int>(syscall(SYS_perf_event_open, &pe, 0, -1, -1, 0));
+#else
+    (void)config;
+    return -1;
+#endif
 }
-void co_body(void* arg) {
-    CoPair& p = *g_pair;
-    const int me = static_cast<int>(reinterpret_cast<intptr_t>(arg));
-    h2j::FrameJob job;
-    for (int r = 0; r < p.reps; r++)
-        for (size_t i = me; i < p.streams->size(); i += 2) {
-            const auto& s = (*p.streams)[i];
-            if (h2j::hevc_parse_picture(s.data(), s.size(), job)) std::abort();
-        }
-    p.co[me].done = true;
-    const int o = me ^ 1;
-    if (!p.co[o].done) {
-        p.cur = o;
-        h2j_ctx_swap(&p.co[me].sp, p.co[o].sp);
-    }
-    h2j_ctx_swap(&p.co[me].sp, p.main.sp);
-    std::abort();
+unsigned long long perf_read(int fd) {
+    unsigned long long v = 0;
+#ifdef __linux__
+    if (fd < 0 || read(fd, &v, sizeof(v)) != static_cast<ssize_t>(sizeof(v))) v = 0;
+#endif
+    return v;
 }
 }  // namespace
 #endif
-#ifdef H2J_CABAC_COUNT
-namespace h2j {
-thread_local unsigned long long g_bins_ctx = 0, g_bins_byp = 0;
+
+// FNV-1a over one picture's records (summed over pictures: an order-independent checksum)
+static unsigned long long job_digest(const h2j::FrameJob& job) {
+    unsigned long long hsh = 1469598103934665603ull;
+    auto mix = [&](const void* p, size_t n) {
+        const unsigned char* q = static_cast<const unsigned char*>(p);
+        for (size_t j = 0; j < n; j++) hsh = (hsh ^ q[j]) * 1099511628211ull;
+    };
+    mix(job.tus.data(), job.tus.size() * sizeof(h2j_tu));
+    mix(job.coefs.data(), job.coefs.size() * sizeof(h2j_coef));
+    mix(job.ctbs.data(), job.ctbs.size() * sizeof(h2j_ctb));
+    mix(job.slices.data(), job.slices.size() * sizeof(h2j_slice));
+    mix(&job.hdr, sizeof(job.hdr));
+    return hsh;
 }
-#endif
 
 int main(int argc, char** argv) {
 #ifdef H2J_SAMPLE
     h2j_sample::start();
 #endif
     if (argc < 2) {
-        std::fprintf(stderr, "usage: parse_bench file... [-r reps] [-t threads] [-d (output digest)]\n");
+        std::fprintf(stderr, "usage: parse_bench file... [-r reps] [-t threads] [-d (output digest)] [-m] [-s] [-p n] [-b (residual breakdown)]\n");
         return 2;
     }
     int reps = 3, threads = 1, pthreads = 1;
-    bool coro = false;
-    (void)coro;
-    bool want_digest = false, want_hist = false, want_min = false;
+    bool want_digest = false, want_hist = false, want_min = false, want_breakdown = false;
     std::vector<std::vector<uint8_t>> streams;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -93,8 +95,8 @@ int main(int argc, char** argv) {
             want_digest = true;
             continue;
         }
-        if (a == "-c") {  // coroutine-paired parse (-DH2J_CORO builds)
-            coro = true;
+        if (a == "-b") {  // residual-syntax breakdown (-DH2J_CABAC_COUNT builds)
+            want_breakdown = true;
             continue;
         }
         if (a == "-m") {  // min-of-reps per stream (robust to a noisy host): sum of per-stream minima
@@ -122,38 +124,75 @@ int main(int argc, char** argv) {
         std::fclose(f);
         streams.push_back(d);
     }
-#ifdef H2J_CORO
-    if (coro) {  // paired (two coroutines) vs sequential, interleaved rounds, one thread
-        for (int round = 0; round < 3; round++) {
-            auto t0 = std::chrono::steady_clock::now();
-            {
-                h2j::FrameJob job;
-                for (int r = 0; r < reps; r++)
-                    for (const auto& s : streams)
-                        if (h2j::hevc_parse_picture(s.data(), s.size(), job)) return 1;
+    if (want_breakdown) {
+#ifdef H2J_CABAC_COUNT
+        // what HEVC residual_coding is fed, per picture and in total over the streams given (one pass on
+        // this thread), the sub-blocks / transform blocks that took each special path of
+        // HevcParser::residual(), and the parse's cycles and branch misses where the kernel allows counters
+        const int fc = perf_open(PERF_COUNT_HW_CPU_CYCLES), fb = perf_open(PERF_COUNT_HW_BRANCH_MISSES);
+        const int perf_errno = fc < 0 ? errno : 0;
+        h2j::FrameJob job;
+        unsigned long long digest = 0;
+        const unsigned long long c0 = perf_read(fc), b0 = perf_read(fb);
+        for (const auto& s : streams) {
+            const int codec = h2j::detect_codec(s.data(), s.size());
+            const int rc = codec == 265 ? h2j::hevc_parse_picture(s.data(), s.size(), job)
+                                        : h2j::h264_parse_picture(s.data(), s.size(), job);
+            if (rc) {
+                std::fprintf(stderr, "parse error %d: %s\n", rc, job.message.c_str());
+                return 1;
             }
-            const double seq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            CoPair p;
-            p.streams = &streams;
-            p.reps = reps;
-            g_pair = &p;
-            h2j::g_h2j_yield = co_yield;
-            h2j_coro::make(p.co[0], 8 << 20, co_body, reinterpret_cast<void*>(0));
-            h2j_coro::make(p.co[1], 8 << 20, co_body, reinterpret_cast<void*>(1));
-            t0 = std::chrono::steady_clock::now();
-            p.cur = 0;
-            h2j_ctx_swap(&p.main.sp, p.co[0].sp);
-            const double par = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            h2j::g_h2j_yield = nullptr;
-            std::free(p.co[0].stack);
-            std::free(p.co[1].stack);
-            const double nf = static_cast<double>(reps) * streams.size();
-            std::printf("round %d: sequential %.4f ms/frame, paired %.4f ms/frame (%+.1f %%)\n", round, seq / nf, par / nf,
-                        100.0 * (par - seq) / seq);
+            digest += job_digest(job);
         }
+        const unsigned long long cyc = perf_read(fc) - c0, brm = perf_read(fb) - b0;
+        const h2j::ResidualStats& r = h2j::g_rstat;
+        const double nf = static_cast<double>(streams.size());
+        std::printf("breakdown of %zu pictures, digest %016llx\n", streams.size(), digest);
+        std::printf("%-44s %14s %14s\n", "item", "per picture", "total");
+        auto row = [&](const char* name, unsigned long long v) { std::printf("%-44s %14.0f %14llu\n", name, v / nf, v); };
+        row("context_bins", h2j::g_bins_ctx);
+        row("bypass_bins", h2j::g_bins_byp);
+        row("tbs_with_residual", r.tbs);
+        row("sub_blocks_visited", r.sb_visited);
+        row("coded_sub_block_flag_bins", r.csbf_bins);
+        row("coded_sub_blocks", r.sb_coded);
+        row("sig_coeff_flag_bins_pos_gt0", r.sig_bins);
+        row("sig_coeff_flag_bins_pos0", r.sig0_bins);
+        row("greater1_bins", r.gt1_bins);
+        row("greater2_bins", r.gt2_bins);
+        row("last_sig_coeff_prefix_bins", r.last_bins);
+        row("coefficients", r.coefs);
+        row("coded_sub_blocks_1_coef", r.sb_by_coefs[0]);
+        row("coded_sub_blocks_2_coefs", r.sb_by_coefs[1]);
+        row("coded_sub_blocks_3_coefs", r.sb_by_coefs[2]);
+        row("coded_sub_blocks_4_7_coefs", r.sb_by_coefs[3]);
+        row("coded_sub_blocks_8plus_coefs", r.sb_by_coefs[4]);
+        row("coefs_with_abs_level_remaining", r.rem_coefs);
+        row("sub_blocks_with_abs_level_remaining", r.rem_sbs);
+        row("sign_batch_sub_blocks", r.sign_batch_sbs);
+        row("sign_single_sub_blocks", r.sign_single_sbs);
+        row("path_one_coef", r.one_coef);
+        row("path_one_coef_escape", r.one_coef_esc);
+        row("path_one_coef_escape_persistent_rice", r.one_coef_esc_price);
+        row("path_one_coef_transform_skip", r.one_coef_tskip);
+        row("path_one_coef_transquant_bypass", r.one_coef_bypass);
+        row("path_one_coef_escape_transform_skip", r.one_coef_esc_tskip);
+        row("path_one_coef_escape_transquant_bypass", r.one_coef_esc_bypass);
+        row("path_dc_only_last_sub_block", r.dc_last_sb);
+        row("path_dc_only_tb", r.dc_only_tb);
+        row("path_sign_pair_single_steps", r.sign_pair);
+        if (fc >= 0 && fb >= 0)
+            std::printf("perf: %.0f cycles, %.0f branch misses per picture; %.2f cycles per bin, %.2f misses per coded sub-block\n",
+                        cyc / nf, brm / nf, cyc / static_cast<double>(h2j::g_bins_ctx + h2j::g_bins_byp),
+                        r.sb_coded ? brm / static_cast<double>(r.sb_coded) : 0.0);
+        else
+            std::printf("perf: hardware counters not available here (perf_event_open: %s); skipped\n", std::strerror(perf_errno));
         return 0;
-    }
+#else
+        std::fprintf(stderr, "-b needs a -DH2J_CABAC_COUNT build\n");
+        return 2;
 #endif
+    }
     if (want_min) {
         h2j::FrameJob job;
         double sum = 0;
@@ -201,17 +240,7 @@ int main(int argc, char** argv) {
             c += job.coefs.size();
             b += s.size();
             if (!want_digest) continue;
-            unsigned long long hsh = 1469598103934665603ull;
-            auto mix = [&](const void* p, size_t n) {
-                const unsigned char* q = static_cast<const unsigned char*>(p);
-                for (size_t j = 0; j < n; j++) hsh = (hsh ^ q[j]) * 1099511628211ull;
-            };
-            mix(job.tus.data(), job.tus.size() * sizeof(h2j_tu));
-            mix(job.coefs.data(), job.coefs.size() * sizeof(h2j_coef));
-            mix(job.ctbs.data(), job.ctbs.size() * sizeof(h2j_ctb));
-            mix(job.slices.data(), job.slices.size() * sizeof(h2j_slice));
-            mix(&job.hdr, sizeof(job.hdr));
-            digest += hsh;
+            digest += job_digest(job);
         }
         tus += t;
         coefs += c;
