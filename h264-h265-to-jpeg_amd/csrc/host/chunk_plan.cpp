@@ -1,0 +1,387 @@
+#include "chunk_plan.h"
+
+#include <algorithm>
+#include <cstring>
+#include <utility>
+
+namespace h2j {
+namespace {
+
+// 256-byte aligned regions handed out front to back (the arena, the staging buffer)
+struct Cursor {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off = align_up(off + bytes, 256);
+        return at;
+    }
+};
+
+// (key, value) pairs -> their values appended to out, smallest key first, equal keys in their order;
+// sorts e in place, so a caller can walk it afterwards in map order
+typedef std::vector<std::pair<long long, uint32_t>> Keyed;
+void append_by_key(Keyed& e, std::vector<uint32_t>& out) {
+    std::stable_sort(e.begin(), e.end(),
+                     [](const Keyed::value_type& a, const Keyed::value_type& b) { return a.first < b.first; });
+    for (const auto& x : e) out.push_back(x.second);
+}
+
+bool k3s_level(const h2j_scaled& sc) { return sc.scale_log2 >= 1 && sc.scale_log2 <= 3; }
+size_t view_blocks(const h2j_scaled& sc) { return static_cast<size_t>(((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4)) * 6; }
+bool banded(const h2j_frame& f) { return f.codec == H2J_CODEC_H264 && f.k1bands > 1; }
+
+// Number the frames' records, and give every frame its views: one per distinct output of its
+// renditions, the unscaled one first.  A view's JPEG size is the cropped picture's, its scaled size or
+// its fit size (K4 / K5 work on that picture)
+void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p) {
+    size_t ntu = 0, ncoef = 0, nctb = 0, nslice = 0, nsl = 0;
+    h2j_gpu_batch& d = p.desc;
+    for (int k = 0; k < p.nf; k++) {
+        const FrameJob& j = jobs[live[k]];
+        d.max_ntu = std::max(d.max_ntu, static_cast<int>(j.tus.size()));
+        h2j_frame& f = p.frames[k];
+        f = j.hdr;
+        f.tu = static_cast<uint32_t>(ntu);
+        f.ntu = static_cast<uint32_t>(j.tus.size());
+        f.coef = static_cast<uint32_t>(ncoef);
+        f.ctb = static_cast<uint32_t>(nctb);
+        f.slice = static_cast<uint32_t>(nslice);
+        f.nslice = static_cast<uint32_t>(j.slices.size());
+        f.sl = static_cast<uint32_t>(nsl);
+        ntu += j.tus.size();
+        ncoef += j.coefs.size();
+        nctb += j.ctbs.size();
+        nslice += j.slices.size();
+        nsl += j.sl.size();
+        // H.264 K1: pictures taller than 1080p run on one workgroup per 16 MB rows
+        // (a single 16-wave workgroup would walk 5+ rows per wave)
+        // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
+        f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
+        f.xline = 0;
+        const size_t v0 = p.scaled.size();
+        p.vfirst[k] = static_cast<int>(v0);
+        auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this output, added if new
+            for (size_t v = v0; v < p.scaled.size(); v++) {
+                const h2j_scaled& sv = p.scaled[v];
+                if (sv.scale_log2 == o.scale_log2 && (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
+                    return static_cast<int>(v);
+            }
+            h2j_scaled sc{};
+            sc.frame = k;
+            sc.scale_log2 = o.scale_log2;
+            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
+            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
+            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
+            p.scaled.push_back(sc);
+            return static_cast<int>(p.scaled.size()) - 1;
+        };
+        for (int r = 0; r < j.nouts; r++)
+            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0) {
+                view_of(j.outs[r]);
+                break;
+            }
+        for (int r = 0; r < j.nouts; r++)
+            if (j.outs[r].error == 0) p.rends.push_back(ChunkPlan::Rend{j.out_base + r, view_of(j.outs[r])});
+        d.max_w = std::max(d.max_w, f.width);
+        d.max_h = std::max(d.max_h, f.height);
+        if (f.codec == H2J_CODEC_HEVC) d.max_ctbs = std::max(d.max_ctbs, f.ctb_w * f.ctb_h);
+    }
+    p.nv = static_cast<int>(p.scaled.size());
+    p.vfirst[p.nf] = p.nv;
+    size_t nblk = 0;
+    for (const h2j_scaled& sc : p.scaled) {
+        d.max_mcu = std::max(d.max_mcu, static_cast<int>(view_blocks(sc) / 6));
+        nblk += view_blocks(sc);
+        p.px += static_cast<double>(sc.jpeg_w) * sc.jpeg_h;
+    }
+    p.tiles = (d.max_mcu * 6 + 255) / 256;
+    p.seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(p.nv);
+    // the records' places in the staging buffer
+    Cursor c;
+    p.at.frames = c.take(p.nf * sizeof(h2j_frame));
+    p.at.tus = c.take(ntu * sizeof(h2j_tu));
+    p.at.coefs = c.take(ncoef * sizeof(h2j_coef));
+    p.at.ctbs = c.take(nctb * sizeof(h2j_ctb));
+    p.at.slices = c.take(nslice * sizeof(h2j_slice));
+    p.at.sl = c.take(nsl + 16);
+    p.at.bytes = c.off;  // the maps follow (layout_maps)
+}
+
+// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
+void layout_arena(ChunkPlan& p) {
+    Cursor a;
+    for (h2j_frame& f : p.frames) {
+        f.maps = a.take(static_cast<size_t>(f.mw) * f.mh * 2);
+        f.ctbrng = a.take(static_cast<size_t>(f.ctb_w) * f.ctb_h * 16);  // [first, first chroma, end, -]
+    }
+    p.jstat_base = a.off;
+    p.jstat_stride = align_up(sizeof(h2j_jstat), 256);
+    for (int v = 0; v < p.nv; v++) {  // one per view; a frame's own is its first view's
+        h2j_scaled& sc = p.scaled[v];
+        sc.jstat = a.take(p.jstat_stride);
+        if (v == p.vfirst[sc.frame]) p.frames[sc.frame].jstat = sc.jstat;
+    }
+    p.zero_bytes = a.off;
+    for (int pass = 0; pass < 2; pass++)
+        for (h2j_frame& f : p.frames) {
+            const size_t pel = f.bit_depth > 8 ? 2 : 1;
+            const size_t ysz = static_cast<size_t>(f.width) * f.height, csz = ysz / 4;
+            f.pic_stride[0] = f.width;
+            f.pic_stride[1] = f.pic_stride[2] = f.width / 2;
+            f.pic_off[0] = 0;
+            f.pic_off[1] = static_cast<int32_t>(ysz);
+            f.pic_off[2] = static_cast<int32_t>(ysz + csz);
+            if (pass == 1 && (f.codec != H2J_CODEC_HEVC || !f.sao_enabled)) {
+                f.pic2 = f.pic;  // no SAO: the deblocked picture is the decoded picture (K3 skips it)
+                continue;
+            }
+            (pass == 0 ? f.pic : f.pic2) = a.take((ysz + 2 * csz) * pel);
+        }
+    for (h2j_scaled& sc : p.scaled) {  // the 8-bit scaled planes K3s / K3r / K3p write and K4 reads (scaled views only)
+        if (sc.scale_log2 == 0) continue;
+        size_t po = 0;
+        for (int c = 0; c < 3; c++) {
+            const int pw = c ? sc.jpeg_w / 2 : sc.jpeg_w, ph = c ? sc.jpeg_h / 2 : sc.jpeg_h;
+            sc.spic_stride[c] = h2j_spic_stride(pw);
+            sc.spic_off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(sc.spic_stride[c]) * ph;
+        }
+        sc.spic = a.take(po);
+    }
+    for (int v = 0; v < p.nv; v++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
+        const h2j_scaled& sc = p.scaled[v];
+        const size_t blocks = view_blocks(sc);
+        p.vjcoef[v] = a.take(std::max(blocks * 64 * 2, (blocks + 255) / 256 * static_cast<size_t>(H2J_JTILE_BYTES)));
+        if (v == p.vfirst[sc.frame]) p.frames[sc.frame].jcoef = p.vjcoef[v];
+    }
+    for (h2j_frame& f : p.frames) {
+        const size_t ysz = static_cast<size_t>(f.width) * f.height;
+        // HEVC residual planes are tiled by K1 quadrant (include/h2j_gpu.h h2j_res_elems: whole
+        // tiles, a little more than the picture); H.264 keeps the picture's raster layout
+        const size_t res_elems = f.codec == H2J_CODEC_HEVC
+                                     ? static_cast<size_t>(h2j_res_elems(f.width, f.height, f.log2ctb))
+                                     : ysz + ysz / 2;
+        f.res = a.take(res_elems * 2);
+        f.aux = a.take(static_cast<size_t>(f.ntu) * 8);
+        if (f.k1bands > 1) {  // per band boundary: K1 1 luma + 2 chroma rows, K2 4 luma + 2x2 chroma rows (uint16)
+            // K1's 8-row bands and K2's 16-row bands use it one after the other
+            const size_t k2b = static_cast<size_t>(f.k1bands - 1) * 6 * f.width * 2;
+            const size_t k1b = static_cast<size_t>((f.ctb_h + 7) / 8 - 1) * 2 * f.width * 2;
+            f.xline = a.take(std::max(k1b, k2b));
+        }
+    }
+    p.arena_bytes = a.off;
+}
+
+// the banded H.264 pictures' bands of `rows` macroblock rows, band-major: (frame << 8) | band
+void band_major(const std::vector<h2j_frame>& frames, int rows, std::vector<uint32_t>& map) {
+    int maxb = 0;
+    for (const h2j_frame& f : frames)
+        if (banded(f)) maxb = std::max(maxb, (f.ctb_h + rows - 1) / rows);
+    for (int bnd = 0; bnd < maxb; bnd++)
+        for (size_t k = 0; k < frames.size(); k++)
+            if (banded(frames[k]) && bnd < (frames[k].ctb_h + rows - 1) / rows)
+                map.push_back((static_cast<uint32_t>(k) << 8) | static_cast<uint32_t>(bnd));
+}
+
+void build_k1_maps(ChunkPlan& p) {
+    // H.264 K1 workgroup map: banded pictures first (their long chains start early), bands in order,
+    // then the others by transform-block count, most first (the dispatcher hands workgroups out in
+    // map order: the heaviest pictures start in the first round, not in the launch's tail)
+    // Banded pictures band-major (every picture's band 0, then every band 1, ...): a band waits on
+    // the band above, and picture-major order had each picture's lower bands holding workgroup
+    // slots while they waited (a batch of 4K H.264 pictures ran at a fraction of the GPU).  A band
+    // still follows the band above it in the map, so it never waits on one not yet dispatched.
+    band_major(p.frames, 16, p.k1map);  // k1bands bands of 16 rows
+    // the same for h2j_k1_recon_h264's 8-wave workgroups: bands of 8 rows (16-row bands took two
+    // row rounds each, so a band below started a whole row time after the band above)
+    band_major(p.frames, 8, p.k1map8);
+    Keyed e;
+    for (int k = 0; k < p.nf; k++) {
+        const h2j_frame& f = p.frames[k];
+        if (f.codec == H2J_CODEC_H264 && !banded(f)) e.emplace_back(-static_cast<long long>(f.ntu), static_cast<uint32_t>(k) << 8);
+    }
+    const size_t nbanded = p.k1map.size();
+    append_by_key(e, p.k1map);
+    p.k1map8.insert(p.k1map8.end(), p.k1map.begin() + static_cast<long>(nbanded), p.k1map.end());
+    // mixed-batch K1 map (h2j_k1_recon_any): every HEVC picture and H.264 band, tallest first so
+    // the longest chains start first; bands of one picture stay in order
+    e.clear();
+    for (int k = 0; k < p.nf; k++) {
+        const h2j_frame& f = p.frames[k];
+        if (f.codec != H2J_CODEC_HEVC) continue;
+        const int rows = f.ctb_h << (f.log2ctb - 4);  // in 16-sample rows
+        if (rows > kK1BandRows) {  // taller than 1088: a 16-wave workgroup per component group
+            e.emplace_back(-2000 - rows, (3u << 30) | (static_cast<uint32_t>(k) << 8) | 0u);
+            e.emplace_back(-2000 - rows, (3u << 30) | (static_cast<uint32_t>(k) << 8) | 1u);
+        } else {
+            e.emplace_back(-rows, (1u << 31) | (static_cast<uint32_t>(k) << 8));
+        }
+    }
+    for (uint32_t m : p.k1map) {
+        const h2j_frame& f = p.frames[m >> 8];
+        e.emplace_back(-std::min(f.ctb_h, 16) - (f.k1bands > 1 ? 1000 : 0), m);
+    }
+    append_by_key(e, p.k1all);
+    for (uint32_t m : p.k1all)
+        if (m & 0x80000000u) p.k1hevc.push_back(m);
+}
+
+// K3 SAO map: the HEVC pictures with SAO, most CTBs first, cut into CTB-count classes (a picture
+// joins the current class while it has more than half the class's CTBs; the last class takes
+// the rest), one launch each, so no class pays for the largest picture's grid width
+void build_sao_classes(ChunkPlan& p) {
+    h2j_gpu_batch& d = p.desc;
+    Keyed e;
+    for (int k = 0; k < p.nf; k++) {
+        const h2j_frame& f = p.frames[k];
+        if (f.codec == H2J_CODEC_HEVC && f.pic2 != f.pic) e.emplace_back(-static_cast<long long>(f.ctb_w * f.ctb_h), static_cast<uint32_t>(k));
+    }
+    append_by_key(e, p.saomap);
+    for (size_t i = 0; i < e.size(); i++) {  // e is now in map order: entry i is saomap[i], its key -CTBs
+        const int ctbs = static_cast<int>(-e[i].first);
+        const bool same = d.sao_groups > 0 && (d.sao_groups == H2J_SAO_GROUPS || 2 * ctbs > d.sao_ctbs[d.sao_groups - 1]);
+        if (!same) {
+            d.sao_first[d.sao_groups] = static_cast<int>(i);
+            d.sao_ctbs[d.sao_groups] = ctbs;
+            d.sao_groups++;
+        }
+        d.sao_count[d.sao_groups - 1]++;
+    }
+}
+
+// K3s / K3r map: the scaled pictures by class (K3s: sample type x scale, K3r: sample type), one
+// launch per class present, its grid as wide as the class's largest picture needs
+// K3p map: a frame with two or more K3s levels among its views gets one h2j_pyramid instead of a K3s
+// entry per level, by class (sample type, coarsest level)
+void build_scale_classes(ChunkPlan& p) {
+    h2j_gpu_batch& d = p.desc;
+    std::vector<int> levels(static_cast<size_t>(p.nf), 0);  // per frame: mask of its K3s levels
+    int npyr = 0;
+    for (int v = 0; v < p.nv && p.nv > p.nf; v++)
+        if (k3s_level(p.scaled[v])) levels[p.scaled[v].frame] |= 1 << p.scaled[v].scale_log2;
+    for (int k = 0; k < p.nf; k++) {
+        if (levels[k] & (levels[k] - 1)) npyr++;
+        else levels[k] = 0;  // one level: K3s
+    }
+    for (int cls = 0; cls < H2J_PYR_CLASSES && npyr; cls++) {
+        d.pyr_first[cls] = static_cast<int>(p.pyrmap.size());
+        for (int k = 0; k < p.nf; k++) {
+            if (!levels[k]) continue;
+            const int kc = (levels[k] & 8) ? 3 : 2;
+            if (2 * (p.frames[k].bit_depth > 8 ? 1 : 0) + kc - 2 != cls) continue;
+            h2j_pyramid py{};
+            py.frame = k;
+            py.mask = levels[k];
+            for (int v = p.vfirst[k]; v < p.vfirst[k + 1]; v++)
+                if (k3s_level(p.scaled[v])) py.lvl[p.scaled[v].scale_log2 - 1] = p.scaled[v];
+            p.pyrmap.push_back(py);
+            d.pyr_count[cls]++;
+            d.pyr_tiles[cls] = std::max(d.pyr_tiles[cls], h2j_k3s_tiles(py.lvl[kc - 1].jpeg_w, py.lvl[kc - 1].jpeg_h));
+        }
+    }
+    for (int cls = 0; cls < H2J_SCALE_CLASSES && p.views; cls++) {
+        d.scale_first[cls] = static_cast<int>(p.scalemap.size());
+        for (const h2j_scaled& sc : p.scaled) {
+            if (sc.scale_log2 == 0 || (levels[sc.frame] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
+            const int hbd = p.frames[sc.frame].bit_depth > 8 ? 1 : 0;
+            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
+            if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
+            p.scalemap.push_back(sc);
+            d.scale_count[cls]++;
+            d.scale_tiles[cls] = std::max(d.scale_tiles[cls], resample ? h2j_k3r_tiles(sc.jpeg_w, sc.jpeg_h) : h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
+        }
+    }
+}
+
+// the maps' places in the staging buffer, behind the records; with scaled pictures or several
+// renditions of a frame the JPEG source views of all frames and the K3s / K3r / K3p maps follow
+void layout_maps(ChunkPlan& p) {
+    Cursor c;
+    c.off = p.at.bytes;
+    p.at.k1map = c.take(p.k1map.size() * 4 + 16);
+    p.at.k1all = c.take(p.k1all.size() * 4 + 16);
+    p.at.sao = c.take(p.saomap.size() * 4 + 16);
+    p.at.k1map8 = c.take(p.k1map8.size() * 4 + 16);
+    p.at.k1hevc = c.take(p.k1hevc.size() * 4 + 16);
+    p.at.jframes = p.at.scale = c.off;
+    if (p.views) {
+        p.at.jframes = c.take(p.nv * sizeof(h2j_frame));
+        p.at.scale = c.take(p.scalemap.size() * sizeof(h2j_scaled) + 16);
+    }
+    p.at.pyr = c.off;
+    if (!p.pyrmap.empty()) c.take(p.pyrmap.size() * sizeof(h2j_pyramid) + 16);
+    p.at.bytes = c.off;
+}
+
+// the descriptor's counts and masks (the maxima and the classes are set where they are found)
+void fill_descriptor(ChunkPlan& p) {
+    h2j_gpu_batch& d = p.desc;
+    d.nframes = p.nf;
+    for (const h2j_frame& f : p.frames) {
+        if (f.codec == H2J_CODEC_HEVC) {
+            d.has_hevc = 1;
+            d.hevc_pels |= (f.bit_depth > 8 || f.bit_depth_c > 8) ? 2 : 1;
+        }
+        if (f.codec != H2J_CODEC_H264) continue;
+        d.has_h264 = 1;
+        if (f.mbaff) d.has_mbaff = 1;
+        else d.h264_pels |= f.bit_depth == 8 ? 1 : 2;
+    }
+    d.k1wgs = static_cast<int32_t>(p.k1map.size());
+    d.k1all_n = static_cast<int32_t>(p.k1all.size());
+    d.k1wgs8 = static_cast<int32_t>(p.k1map8.size());
+    d.k1hevc_n = static_cast<int32_t>(p.k1hevc.size());
+    // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
+    // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
+    for (const h2j_scaled& sc : p.scaled)
+        d.k4a_frames += (h2j_sao_folds_variance(p.frames[sc.frame]) && sc.scale_log2 == 0) ? 0 : 1;
+}
+
+}  // namespace
+
+// An unscaled frame is its own view; a scaled frame's view is the 8-bit picture K3s, K3r or K3p writes
+// at its h2j_scaled record's spic (include/h2j_gpu.h h2j_gpu_batch.jframes).  Every view has its own
+// jcoef / tile region and jstat (the first view keeps the frame's own).
+h2j_frame ChunkPlan::view(int v) const {
+    const h2j_scaled& sc = scaled[v];
+    h2j_frame f = frames[sc.frame];
+    f.jcoef = vjcoef[v];
+    f.jstat = sc.jstat;
+    if (sc.scale_log2 == 0) return f;
+    f.pic = f.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
+    f.crop_x = f.crop_y = 0;
+    f.out_w = sc.jpeg_w;
+    f.out_h = sc.jpeg_h;
+    f.bit_depth = f.bit_depth_c = 8;
+    for (int c = 0; c < 3; c++) {
+        f.pic_stride[c] = sc.spic_stride[c];
+        f.pic_off[c] = sc.spic_off[c];
+    }
+    return f;
+}
+
+void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p) {
+    p.nf = static_cast<int>(live.size());
+    p.frames.resize(static_cast<size_t>(p.nf));
+    p.vfirst.assign(static_cast<size_t>(p.nf) + 1, 0);
+    for (auto* m : {&p.k1map, &p.k1map8, &p.k1all, &p.k1hevc, &p.saomap}) m->clear();
+    p.scaled.clear();
+    p.rends.clear();
+    p.scalemap.clear();
+    p.pyrmap.clear();
+    p.px = 0;
+    std::memset(&p.desc, 0, sizeof(p.desc));
+    number_frames_and_views(jobs, live, p);
+    // scaled pictures present, or several renditions of a frame: a views array is uploaded
+    p.views = p.nv > p.nf || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; });
+    p.vjcoef.resize(static_cast<size_t>(p.nv));
+    layout_arena(p);
+    build_k1_maps(p);
+    build_sao_classes(p);
+    build_scale_classes(p);
+    layout_maps(p);
+    fill_descriptor(p);
+}
+
+}  // namespace h2j

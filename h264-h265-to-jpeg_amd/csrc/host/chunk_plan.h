@@ -1,0 +1,67 @@
+// The plan of one GPU chunk: everything the engine decides about a set of parsed pictures before it
+// touches a buffer -- frames and views, the arena layout, the workgroup maps, the staging layout and the
+// scalar fields of the batch descriptor.  Pure host arithmetic on the job records: no GPU call.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "h2j_gpu.h"
+#include "job.h"
+
+namespace h2j {
+
+// H.264 pictures with more MB rows than this are reconstructed by several K1 workgroups
+constexpr int kK1BandRows = 68;
+
+// upper bound of one block's entropy-coded size (code lengths <= 16, values <= 16 bits)
+constexpr size_t kSegBytesPerBlock = 272;
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct ChunkPlan {
+    // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
+    // is (frame, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
+    // the first view of a frame -- its unscaled rendition if it has one -- keeps the frame's own jcoef
+    // and jstat.  One rendition per item: nv == nf, view k is frame k
+    int nf = 0, nv = 0;
+    std::vector<h2j_frame> frames;   // per frame: the job's header with its record ranges and arena offsets
+    std::vector<h2j_scaled> scaled;  // per view: its JPEG size and, for a scaled output, its scaled planes
+    std::vector<uint64_t> vjcoef;    // per view: its jcoef / tile region
+    std::vector<int> vfirst;         // per frame: its first view (nf + 1 entries)
+    struct Rend {
+        int out, view;  // index in the batch's output arrays; the view that holds its JPEG
+    };
+    std::vector<Rend> rends;  // the chunk's renditions (those with valid options), frame-major
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
+    size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
+    size_t seg_cap = 0;  // payload pool bytes (K5)
+    int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)
+    double px = 0;       // JPEG pixels of the chunk (payload estimate)
+
+    // workgroup maps (include/h2j_gpu.h h2j_gpu_batch), uploaded behind the records
+    std::vector<uint32_t> k1map, k1map8, k1all, k1hevc, saomap;
+    std::vector<h2j_scaled> scalemap;
+    std::vector<h2j_pyramid> pyrmap;
+    bool views = false;  // a views array is uploaded (a scaled picture, or several renditions of a frame)
+
+    // staging layout: byte offset of each array in the one buffer the chunk uploads
+    struct Staging {
+        size_t frames = 0, tus = 0, coefs = 0, ctbs = 0, slices = 0, sl = 0, k1map = 0, k1all = 0, sao = 0, k1map8 = 0,
+               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, bytes = 0;
+    } at;
+
+    // the descriptor's scalar fields (counts, maxima, codec / sample-type masks, classes); its pointers,
+    // jpeg_dense and seg_cap are the engine's to fill once it has the buffers
+    h2j_gpu_batch desc{};
+
+    // the JPEG source view of view v: what K4 (variance, FDCT) and K5 read as "the picture"
+    h2j_frame view(int v) const;
+};
+
+// Plan the chunk of jobs[live[0..]] (parsed jobs, each with at least one output) into p; p's vectors are
+// reused from chunk to chunk.
+void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p);
+
+}  // namespace h2j

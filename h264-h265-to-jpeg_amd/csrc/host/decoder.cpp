@@ -53,15 +53,12 @@ namespace {
 struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
-    // scaled / exact-size output (h2j_h265_to_jpeg_mem_scaled, _fit); all 0: the decoded size
-    h2j_out_opts2 opts = {0, 0, 0, 0, 0, {0, 0, 0}};
-    // several renditions of the picture (h2j_h265_to_jpeg_mem_multi): their options, and per rendition
-    // the JPEG and status; empty: the one output `opts` names
-    std::vector<h2j_out_opts2> ropts;
+    // the options of the picture's renditions: one (all 0: the decoded size; h2j_h265_to_jpeg_mem_scaled,
+    // _fit) or several (h2j_h265_to_jpeg_mem_multi); per rendition the JPEG and status once the batch ran
+    std::vector<h2j_out_opts2> opts{h2j_out_opts2{0, 0, 0, 0, 0, {0, 0, 0}}};
     std::vector<std::vector<uint8_t>> jpegs;
     std::vector<int> rstatus;
-    std::vector<uint8_t> jpeg;
-    int status = 0;
+    int status = 0;  // of the first rendition, which is all a plain caller asks for (-1: the batch did not run)
     std::string error;
     bool done = false;
 };
@@ -116,10 +113,11 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
     return out;
 }
 
-// run one batch in which some request has several renditions: every picture is decoded once
-// (h2j_engine_transcode_multi; a plain request is an item with one rendition)
-void run_batch_multi(h2j_engine* e, std::vector<Request*>& batch) {
+// run one batch (caller holds no lock); fills jpegs / rstatus / status / error of each request.  Every
+// picture is decoded once (h2j_engine_transcode_multi; a plain request is an item with one rendition)
+void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
+    if (n == 0) return;
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> sizes(n);
     std::vector<int32_t> nrend(n);
@@ -130,10 +128,9 @@ void run_batch_multi(h2j_engine* e, std::vector<Request*>& batch) {
         const Request* q = batch[i];
         ptrs[i] = q->data;
         sizes[i] = q->size;
-        nrend[i] = q->ropts.empty() ? 1 : static_cast<int32_t>(q->ropts.size());
+        nrend[i] = static_cast<int32_t>(q->opts.size());
         base[i + 1] = base[i] + nrend[i];
-        if (q->ropts.empty()) opts.push_back(q->opts);
-        else opts.insert(opts.end(), q->ropts.begin(), q->ropts.end());
+        opts.insert(opts.end(), q->opts.begin(), q->opts.end());
         cap += (q->size * 4 + (2u << 20)) * static_cast<size_t>(nrend[i]);
     }
     const int total = base[n];
@@ -152,67 +149,21 @@ void run_batch_multi(h2j_engine* e, std::vector<Request*>& batch) {
     }
     for (int i = 0; i < n; i++) {
         Request* q = batch[i];
-        const bool multi = !q->ropts.empty();
-        if (multi) {
-            q->jpegs.assign(static_cast<size_t>(nrend[i]), std::vector<uint8_t>());
-            q->rstatus.assign(static_cast<size_t>(nrend[i]), 0);
-        }
-        q->status = 0;
+        q->jpegs.assign(static_cast<size_t>(nrend[i]), std::vector<uint8_t>());
+        q->rstatus.assign(static_cast<size_t>(nrend[i]), 0);
         for (int k = 0; k < nrend[i]; k++) {
             const int o = base[i] + k;
             int st = status[o];
             if (r != 0 && st == 0) st = r;
             if (st == 0) {
-                std::vector<uint8_t>& dst = multi ? q->jpegs[k] : q->jpeg;
-                dst.assign(out.begin() + static_cast<long>(off[o]), out.begin() + static_cast<long>(off[o] + len[o]));
+                q->jpegs[k].assign(out.begin() + static_cast<long>(off[o]), out.begin() + static_cast<long>(off[o] + len[o]));
             } else if (q->error.empty()) {
                 const char* m = status[o] != 0 ? h2j_engine_frame_error(e, o) : "";
                 q->error = (m && *m) ? m : h2j_engine_error(e);
             }
-            if (multi) q->rstatus[k] = st;
-            else q->status = st;
+            q->rstatus[k] = st;
         }
-    }
-}
-
-// run one batch (caller holds no lock); fills jpeg / status / error of each request
-void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
-    const int n = static_cast<int>(batch.size());
-    if (n == 0) return;
-    for (const Request* q : batch)
-        if (!q->ropts.empty()) return run_batch_multi(e, batch);
-    std::vector<const uint8_t*> ptrs(n);
-    std::vector<size_t> sizes(n), off(n), len(n);
-    std::vector<int> status(n);
-    std::vector<h2j_out_opts2> opts(n);
-    size_t cap = 8u << 20;
-    for (int i = 0; i < n; i++) {
-        opts[i] = batch[i]->opts;
-        ptrs[i] = batch[i]->data;
-        sizes[i] = batch[i]->size;
-        cap += batch[i]->size * 4 + (2u << 20);
-    }
-    std::vector<uint8_t> out;
-    int r = -1;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        out.resize(cap);
-        r = h2j_engine_transcode_opts2(e, n, ptrs.data(), sizes.data(), opts.data(), out.data(), cap, off.data(),
-                                       len.data(), status.data());
-        bool small = false;
-        for (int i = 0; i < n; i++) small = small || status[i] == -50;
-        if (!small) break;
-        cap *= 4;
-    }
-    for (int i = 0; i < n; i++) {
-        Request* q = batch[i];
-        q->status = status[i];
-        if (r != 0 && status[i] == 0) q->status = r;
-        if (q->status == 0) {
-            q->jpeg.assign(out.begin() + static_cast<long>(off[i]), out.begin() + static_cast<long>(off[i] + len[i]));
-        } else {
-            const char* m = status[i] != 0 ? h2j_engine_frame_error(e, i) : "";
-            q->error = (m && *m) ? m : h2j_engine_error(e);
-        }
+        q->status = q->rstatus[0];
     }
 }
 
@@ -303,7 +254,7 @@ bool Decoder::H265ToJpeg(const char* const in, const char* const out) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return false;
     }
-    const std::vector<uint8_t>& jpeg = req.jpeg;
+    const std::vector<uint8_t>& jpeg = req.jpegs[0];
     FILE* f = fopen(out, "wb+");
     if (!f) {
         LOG("failed to encode Yuv to Jpeg: cannot open %s", out);
@@ -337,16 +288,17 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts = opts;
+    req.opts[0] = opts;
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
     }
-    uint8_t* p = static_cast<uint8_t*>(malloc(req.jpeg.size()));
+    const std::vector<uint8_t>& got = req.jpegs[0];
+    uint8_t* p = static_cast<uint8_t*>(malloc(got.size()));
     if (!p) return -1;
-    std::memcpy(p, req.jpeg.data(), req.jpeg.size());
+    std::memcpy(p, got.data(), got.size());
     *jpeg = p;
-    *jpeg_len = req.jpeg.size();
+    *jpeg_len = got.size();
     return 0;
 }
 
@@ -373,7 +325,7 @@ extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int 
     Request req;
     req.data = data;
     req.size = size;
-    req.ropts.assign(opts, opts + nrend);
+    req.opts.assign(opts, opts + nrend);
     transcode_shared(req);
     if (req.rstatus.size() != static_cast<size_t>(nrend)) {  // the batch did not run (no HIP device)
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
@@ -431,9 +383,10 @@ extern "C" int h2j_h265_to_jpeg_batch(const char* const* in_paths, const char* c
             LOG("failed to encode Yuv to Jpeg: cannot open %s", out_paths[i]);
             continue;
         }
-        const size_t w = fwrite(q.jpeg.data(), 1, q.jpeg.size(), f);
+        const std::vector<uint8_t>& jpeg = q.jpegs[0];
+        const size_t w = fwrite(jpeg.data(), 1, jpeg.size(), f);
         fclose(f);
-        if (w != q.jpeg.size()) {
+        if (w != jpeg.size()) {
             LOG("failed to write Jpeg file %s", out_paths[i]);
             continue;
         }

@@ -36,6 +36,7 @@
 
 #include "affinity.h"
 #include "bitstream.h"
+#include "chunk_plan.h"
 #include "h2j.h"
 #include "h2j_gpu.h"
 #include "job.h"
@@ -47,8 +48,6 @@ namespace {
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 class ThreadPool {
 public:
@@ -177,11 +176,19 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
+// Output options: h2j_out_opts2 is the engine's one option type (an h2j_out_opts item has the fit fields 0)
+const h2j_out_opts2 kPlainOutput = {0, 0, 0, 0, 0, {0, 0, 0}};  // the JPEG at the decoded size
+std::vector<h2j_out_opts2> opts2_of(int n, const h2j_out_opts* o) {  // o null: all plain
+    std::vector<h2j_out_opts2> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+    for (int i = 0; o && i < n; i++) {
+        v[i].scale_log2 = o[i].scale_log2;
+        v[i].max_dim = o[i].max_dim;
+    }
+    return v;
+}
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
 // max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does).
-// Exact-size output (h2j_out_opts2, the engine's one option type; an h2j_out_opts item has the fit
-// fields 0): the size h2j_fit_size gives.
-h2j_out_opts2 opts2_of(const h2j_out_opts& o) { return h2j_out_opts2{o.scale_log2, o.max_dim, 0, 0, 0, {0, 0, 0}}; }
+// Exact-size output (h2j_out_opts2): the size h2j_fit_size gives.
 bool fit_valid(int fit_w, int fit_h, int flags) {
     return (fit_w == 0 || (fit_w >= 2 && fit_w <= 65535)) && (fit_h == 0 || (fit_h >= 2 && fit_h <= 65535)) &&
            (flags & ~H2J_FIT_STRETCH) == 0 && !((flags & H2J_FIT_STRETCH) && fit_w == 0 && fit_h == 0);
@@ -197,24 +204,24 @@ int resolve_scale(const h2j_out_opts2& o, int w, int h) {
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
     return k;
 }
-// the job's output size from valid options and the parsed size.  A fit that resolves to the picture's
-// own size is the unscaled job; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k: the
-// resampler's arithmetic reduces to K3s's there) is the scaled job of that k; K3r gets the rest
-void resolve_output(const h2j_out_opts2& o, FrameJob& job) {
-    const int w = job.hdr.out_w, h = job.hdr.out_h;
-    job.scale_log2 = resolve_scale(o, w, h);
-    job.fit_w = job.fit_h = 0;
+// the output of a w x h picture (its parsed, cropped size) with valid options.  A fit that resolves to the
+// picture's own size is the unscaled output; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k:
+// the resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest
+FrameJob::Output resolve_output(const h2j_out_opts2& o, int w, int h) {
+    FrameJob::Output out;
+    out.scale_log2 = resolve_scale(o, w, h);
     int ow = w, oh = h;
-    if ((o.fit_w == 0 && o.fit_h == 0) || h2j_fit_size(w, h, o.fit_w, o.fit_h, o.flags, &ow, &oh) != 0) return;
-    if (ow == w && oh == h) return;
+    if ((o.fit_w == 0 && o.fit_h == 0) || h2j_fit_size(w, h, o.fit_w, o.fit_h, o.flags, &ow, &oh) != 0) return out;
+    if (ow == w && oh == h) return out;
     for (int k = 1; k <= 3; k++)
         if ((ow << k) == w && (oh << k) == h) {
-            job.scale_log2 = k;
-            return;
+            out.scale_log2 = k;
+            return out;
         }
-    job.scale_log2 = H2J_SCALE_RESAMPLE;
-    job.fit_w = ow;
-    job.fit_h = oh;
+    out.scale_log2 = H2J_SCALE_RESAMPLE;
+    out.fit_w = ow;
+    out.fit_h = oh;
+    return out;
 }
 std::string out_opts_message(const h2j_out_opts2& o) {
     return "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
@@ -222,104 +229,69 @@ std::string out_opts_message(const h2j_out_opts2& o) {
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
            " (stretch needs a size), reserved " + ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
 }
-// parse one item of a batch with its output options; invalid options fail the item alone
-int parse_item(const uint8_t* d, size_t n, const h2j_out_opts2& o, FrameJob& job) {
-    if (!out_opts_valid(o)) {
-        job.clear();
-        job.error = H2J_ERR_OUT_OPTS;
-        job.message = out_opts_message(o);
-        return job.error;
+// the outputs of a parsed job: every rendition's is resolved on its own, and invalid options fail that
+// rendition alone
+void resolve_outputs(const h2j_out_opts2* o, int nr, FrameJob& job) {
+    job.nouts = nr;
+    for (int r = 0; r < nr; r++) {
+        job.outs[r] = FrameJob::Output();
+        if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h);
+        else job.outs[r].error = H2J_ERR_OUT_OPTS;
     }
-    const int r = parse_any(d, n, job);
-    if (r == 0) resolve_output(o, job);  // needs the parsed size
-    return r;
 }
-// the same for an item with nr renditions (h2j_engine_transcode_multi): one parse; every rendition's
-// output is resolved on its own, and invalid options fail that rendition alone (the item is not parsed
-// when none is valid).  *ran: the entropy decode ran
+// parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
+// is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
 int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts2* o, int nr, FrameJob& job, bool* ran) {
-    *ran = false;
-    int valid = 0;
-    for (int r = 0; r < nr; r++) valid += out_opts_valid(o[r]) ? 1 : 0;
-    if (!valid) {
+    *ran = std::any_of(o, o + nr, out_opts_valid);
+    if (!*ran) {
         job.clear();
         job.error = H2J_ERR_OUT_OPTS;
         job.message = out_opts_message(o[0]);
         return job.error;
     }
-    *ran = true;
     const int rc = parse_any(d, n, job);
-    if (rc) return rc;
-    job.outs.resize(static_cast<size_t>(nr));
-    for (int r = 0; r < nr; r++) {
-        FrameJob::Output& out = job.outs[static_cast<size_t>(r)];
-        out = FrameJob::Output();
-        if (!out_opts_valid(o[r])) {
-            out.error = H2J_ERR_OUT_OPTS;
-            continue;
-        }
-        resolve_output(o[r], job);
-        out.scale_log2 = job.scale_log2;
-        out.fit_w = job.fit_w;
-        out.fit_h = job.fit_h;
-    }
-    job.scale_log2 = job.fit_w = job.fit_h = 0;
-    return 0;
-}
-
-// The JPEG source view of a frame: what K4 (variance, FDCT) and K5 read as "the picture"
-// (include/h2j_gpu.h h2j_gpu_batch.jframes).  An unscaled frame is its own view; a scaled frame's
-// view is the 8-bit picture K3s or K3r writes at its h2j_scaled record's spic.
-// A frame with several renditions has one view per distinct output, each with its own jcoef / tile
-// region and jstat (the first view keeps the frame's own).
-h2j_frame jpeg_view(const h2j_frame& f, const h2j_scaled& sc, uint64_t jcoef) {
-    h2j_frame v = f;
-    v.jcoef = jcoef;
-    v.jstat = sc.jstat;
-    if (sc.scale_log2 == 0) return v;
-    v.pic = v.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
-    v.crop_x = v.crop_y = 0;
-    v.out_w = sc.jpeg_w;
-    v.out_h = sc.jpeg_h;
-    v.bit_depth = v.bit_depth_c = 8;
-    for (int c = 0; c < 3; c++) {
-        v.pic_stride[c] = sc.spic_stride[c];
-        v.pic_off[c] = sc.spic_off[c];
-    }
-    return v;
+    if (rc == 0) resolve_outputs(o, nr, job);  // needs the parsed size
+    return rc;
 }
 
 }  // namespace
 
+// The events of a chunk, in the order its stream reaches them
+enum {
+    EV_BEGIN,       // before the H2D copy
+    EV_H2D,         // after it; the wait for the other slot's kernels follows
+    EV_GPU_BEGIN,   // after that wait: the chunk's GPU work starts with the arena fill
+    EV_ZEROED,
+    EV_K0,
+    EV_K1,
+    EV_K2,
+    EV_K3,
+    EV_SCALE,       // after K3s / K3r / K3p (scaled output)
+    EV_K4,
+    EV_K5,          // the last kernel: the other slot's next chunk waits for it
+    EV_STATS,       // after the stats D2H
+    EV_PAY_BEGIN,   // around the in-stream payload D2H
+    EV_PAY_END,
+    EV_PAY2_BEGIN,  // around a second (whole) payload copy (sync)
+    EV_PAY2_END,
+    EV_END,
+    EV_N
+};
+
 // One in-flight chunk: its stream, buffers and layout.
 struct Slot {
     void* stream = nullptr;
-    // 9: after the stats D2H, 10 / 11: around the in-stream payload D2H, 12 / 13: around the wait for
-    // the other slot, 14 / 15: around a second (whole) payload copy, 16: after K3s / K3r (scaled output)
-    void* ev[17] = {nullptr};
+    void* ev[EV_N] = {nullptr};
     size_t pay_pre = 0;        // payload bytes already copied in-stream by enqueue() (estimated, <= h_seg's capacity)
-    double px = 0;             // output pixels of the chunk (payload estimate)
     int small_runs = 0;        // consecutive chunks whose payload used < 1/4 of h_seg (shrink after 8)
     size_t small_max = 0;      // the largest payload of that run
     DevBuf d_in, d_arena, d_seg, d_scratch;
     HostBuf h_in, h_js, h_seg;
-    std::vector<h2j_frame> frames;
-    // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
-    // is (frame, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
-    // the first view of a frame -- its unscaled rendition if it has one -- keeps the frame's own jcoef
-    // and jstat.  One rendition per item: nv == nf, view k is frame k
-    std::vector<h2j_scaled> scaled;  // per view: its JPEG size and, for a scaled output, its scaled planes
-    std::vector<uint64_t> vjcoef;    // per view: its jcoef / tile region
-    std::vector<int> vfirst;         // per frame: its first view (nf + 1 entries)
-    struct Rend {
-        int out, view;  // index in the batch's output arrays; the view that holds its JPEG
-    };
-    std::vector<Rend> rends;  // the chunk's renditions (those with valid options), frame-major
+    ChunkPlan plan;  // the chunk's frames and views, layouts and maps (chunk_plan.h)
     std::vector<int> live;  // job index of each frame of the chunk
     std::vector<FrameJob>* jobs = nullptr;  // the job set `live` indexes
     h2j_gpu_batch batch{};   // K0 .. K3, K3s / K3r / K3p: the frames
     h2j_gpu_batch jbatch{};  // K4, K5: the views (== batch when nv == nf)
-    size_t zero_bytes = 0, jcoef_base = 0, jcoef_bytes = 0, jstat_base = 0, jstat_stride = 0;
     int stages = 0;
     bool entropy = false, pending = false;
 
@@ -350,12 +322,6 @@ enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEM
        ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s + K3r + K3p
 // ST_RENDITIONS: JPEG outputs of the batch (ST_FRAMES: decoded pictures); ST_PARSED: pictures whose entropy decode ran
 
-// H.264 pictures with more MB rows than this are reconstructed by several K1 workgroups
-constexpr int kK1BandRows = 68;
-
-// upper bound of one block's entropy-coded size (code lengths <= 16, values <= 16 bits)
-constexpr size_t kSegBytesPerBlock = 272;
-
 struct ChunkTime {
     int frames = 0;
     double k1_ms = 0, kernels_ms = 0;  // K1 launch; K0..K5 (HIP events on the chunk's stream)
@@ -372,9 +338,9 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts2> opts;           // per-item output options (empty: all zero); multi: per rendition, item-major
-    std::vector<int> rbase;                    // multi (h2j_engine_submit_multi): first rendition of each item, n + 1 entries; else empty
-    int nout = 0;                              // entries of out_off / out_len / status: n, or the renditions of a multi batch
+    std::vector<h2j_out_opts2> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
+    int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
     std::vector<int> bounds;                   // parse chunks: index ranges
     std::vector<int> chunk_of;
@@ -477,489 +443,152 @@ struct Engine {
     // `after`: the other slot, when its kernels are still in flight -- this slot's kernels start once
     // they have finished (its copies and the host's assembly still overlap them)
     int enqueue(Slot& s, int stages, bool entropy, bool pool_free = true, const Slot* after = nullptr);  // s.jobs must be set
+    // enqueue's steps, after the plan (ChunkPlan): buffers, staging bytes, descriptors, launches, payload copy
+    int ensure_buffers(Slot& s);
+    void pack_staging(Slot& s, bool pool_free);
+    void fill_descriptors(Slot& s);
+    int launch(Slot& s, const Slot* after);
+    int enqueue_payload_copy(Slot& s);
     // Wait for slot s and copy its payloads down (entropy chunks).
     int sync(Slot& s);
 };
 
-int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slot* after) {
-    const int nf = static_cast<int>(s.live.size());
-    s.stages = stages;
-    s.entropy = entropy;
-    s.pending = false;
-    if (nf == 0) return 0;
-    s.frames.resize(nf);
-    s.scaled.clear();
-    s.rends.clear();
-    s.vfirst.assign(static_cast<size_t>(nf) + 1, 0);
-    size_t ntu = 0, ncoef = 0, nctb = 0, nslice = 0, nsl = 0, nblk = 0;
-    int max_w = 0, max_h = 0, max_mcu = 0, max_ntu = 0, max_ctbs = 0;
-    const std::vector<FrameJob>& jobs = *s.jobs;
-    for (int k = 0; k < nf; k++) {
-        const FrameJob& j = jobs[s.live[k]];
-        max_ntu = std::max(max_ntu, static_cast<int>(j.tus.size()));
-        h2j_frame f = j.hdr;
-        f.tu = static_cast<uint32_t>(ntu);
-        f.ntu = static_cast<uint32_t>(j.tus.size());
-        f.coef = static_cast<uint32_t>(ncoef);
-        f.ctb = static_cast<uint32_t>(nctb);
-        f.slice = static_cast<uint32_t>(nslice);
-        f.nslice = static_cast<uint32_t>(j.slices.size());
-        f.sl = static_cast<uint32_t>(nsl);
-        ntu += j.tus.size();
-        ncoef += j.coefs.size();
-        nctb += j.ctbs.size();
-        nslice += j.slices.size();
-        nsl += j.sl.size();
-        // H.264 K1: pictures taller than 1080p run on one workgroup per 16 MB rows
-        // (a single 16-wave workgroup would walk 5+ rows per wave)
-        // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
-        f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
-        f.xline = 0;
-        // the JPEG's size: the cropped picture, its scaled size or its fit size (K4 / K5 work on that picture)
-        // the frame's views: one per distinct output of its renditions, the unscaled one first
-        const size_t v0 = s.scaled.size();
-        s.vfirst[k] = static_cast<int>(v0);
-        FrameJob::Output one;
-        one.scale_log2 = j.scale_log2;
-        one.fit_w = j.fit_w;
-        one.fit_h = j.fit_h;
-        const FrameJob::Output* outs = j.outs.empty() ? &one : j.outs.data();
-        const int nr = j.outs.empty() ? 1 : static_cast<int>(j.outs.size());
-        auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this output, added if new
-            for (size_t v = v0; v < s.scaled.size(); v++) {
-                const h2j_scaled& sv = s.scaled[v];
-                if (sv.scale_log2 == o.scale_log2 && (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
-                    return static_cast<int>(v);
-            }
-            h2j_scaled sc{};
-            sc.frame = k;
-            sc.scale_log2 = o.scale_log2;
-            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
-            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
-            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
-            s.scaled.push_back(sc);
-            const int mcu = ((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4);
-            max_mcu = std::max(max_mcu, mcu);
-            nblk += static_cast<size_t>(mcu) * 6;
-            return static_cast<int>(s.scaled.size()) - 1;
-        };
-        for (int r = 0; r < nr; r++)
-            if (outs[r].error == 0 && outs[r].scale_log2 == 0) {
-                view_of(outs[r]);
-                break;
-            }
-        for (int r = 0; r < nr; r++)
-            if (outs[r].error == 0) s.rends.push_back(Slot::Rend{j.out_base + r, view_of(outs[r])});
-        s.frames[k] = f;
-        max_w = std::max(max_w, f.width);
-        if (f.codec == H2J_CODEC_HEVC) max_ctbs = std::max(max_ctbs, f.ctb_w * f.ctb_h);
-        max_h = std::max(max_h, f.height);
-    }
-    const int nv = static_cast<int>(s.scaled.size());
-    s.vfirst[nf] = nv;
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
-    size_t off = 0;
-    for (int k = 0; k < nf; k++) {
-        h2j_frame& f = s.frames[k];
-        f.maps = off;
-        off = align_up(off + static_cast<size_t>(f.mw) * f.mh * 2, 256);
-        f.ctbrng = off;
-        off = align_up(off + static_cast<size_t>(f.ctb_w) * f.ctb_h * 16, 256);  // [first, first chroma, end, -]
-    }
-    s.jstat_base = off;
-    s.jstat_stride = align_up(sizeof(h2j_jstat), 256);
-    for (int v = 0; v < nv; v++) {  // one per view; a frame's own is its first view's
-        s.scaled[v].jstat = off;
-        if (v == s.vfirst[s.scaled[v].frame]) s.frames[s.scaled[v].frame].jstat = off;
-        off += s.jstat_stride;
-    }
-    s.zero_bytes = off;
-    for (int pass = 0; pass < 2; pass++)
-        for (int k = 0; k < nf; k++) {
-            h2j_frame& f = s.frames[k];
-            const size_t pel = f.bit_depth > 8 ? 2 : 1;
-            const size_t ysz = static_cast<size_t>(f.width) * f.height, csz = ysz / 4;
-            f.pic_stride[0] = f.width;
-            f.pic_stride[1] = f.pic_stride[2] = f.width / 2;
-            f.pic_off[0] = 0;
-            f.pic_off[1] = static_cast<int32_t>(ysz);
-            f.pic_off[2] = static_cast<int32_t>(ysz + csz);
-            if (pass == 1 && (f.codec != H2J_CODEC_HEVC || !f.sao_enabled)) {
-                f.pic2 = f.pic;  // no SAO: the deblocked picture is the decoded picture (K3 skips it)
-                continue;
-            }
-            if (pass == 0) f.pic = off; else f.pic2 = off;
-            off = align_up(off + (ysz + 2 * csz) * pel, 256);
-        }
-    int nscaled = 0;
-    for (int k = 0; k < nv; k++) {  // the 8-bit scaled planes K3s / K3r / K3p write and K4 reads (scaled views only)
-        h2j_scaled& sc = s.scaled[k];
-        if (sc.scale_log2 == 0) continue;
-        nscaled++;
-        sc.spic = off;
-        size_t po = 0;
-        for (int c = 0; c < 3; c++) {
-            const int pw = c ? sc.jpeg_w / 2 : sc.jpeg_w, ph = c ? sc.jpeg_h / 2 : sc.jpeg_h;
-            sc.spic_stride[c] = h2j_spic_stride(pw);
-            sc.spic_off[c] = static_cast<int32_t>(po);
-            po += static_cast<size_t>(sc.spic_stride[c]) * ph;
-        }
-        off = align_up(off + po, 256);
-    }
-    s.jcoef_base = off;
-    s.vjcoef.resize(static_cast<size_t>(nv));
-    for (int k = 0; k < nv; k++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
-        s.vjcoef[k] = off;
-        if (k == s.vfirst[s.scaled[k].frame]) s.frames[s.scaled[k].frame].jcoef = off;
-        const size_t blocks = static_cast<size_t>(((s.scaled[k].jpeg_w + 15) >> 4) * ((s.scaled[k].jpeg_h + 15) >> 4)) * 6;
-        off = align_up(off + std::max(blocks * 64 * 2, (blocks + 255) / 256 * static_cast<size_t>(H2J_JTILE_BYTES)), 256);
-    }
-    s.jcoef_bytes = off - s.jcoef_base;
-    for (int k = 0; k < nf; k++) {
-        h2j_frame& f = s.frames[k];
-        const size_t ysz = static_cast<size_t>(f.width) * f.height;
-        // HEVC residual planes are tiled by K1 quadrant (include/h2j_gpu.h h2j_res_elems: whole
-        // tiles, a little more than the picture); H.264 keeps the picture's raster layout
-        const size_t res_elems = f.codec == H2J_CODEC_HEVC
-                                     ? static_cast<size_t>(h2j_res_elems(f.width, f.height, f.log2ctb))
-                                     : ysz + ysz / 2;
-        f.res = off;
-        off = align_up(off + res_elems * 2, 256);
-        f.aux = off;
-        off = align_up(off + static_cast<size_t>(f.ntu) * 8, 256);
-        if (f.k1bands > 1) {  // per band boundary: K1 1 luma + 2 chroma rows, K2 4 luma + 2x2 chroma rows (uint16)
-            f.xline = off;   // K1's 8-row bands and K2's 16-row bands use it one after the other
-            const size_t k2b = static_cast<size_t>(f.k1bands - 1) * 6 * f.width * 2;
-            const size_t k1b = static_cast<size_t>((f.ctb_h + 7) / 8 - 1) * 2 * f.width * 2;
-            off = align_up(off + std::max(k1b, k2b), 256);
-        }
-    }
-    const size_t arena_bytes = off;
-    // input staging
-    const size_t o_frames = 0;
-    const size_t o_tus = align_up(o_frames + nf * sizeof(h2j_frame), 256);
-    const size_t o_coefs = align_up(o_tus + ntu * sizeof(h2j_tu), 256);
-    const size_t o_ctbs = align_up(o_coefs + ncoef * sizeof(h2j_coef), 256);
-    const size_t o_slices = align_up(o_ctbs + nctb * sizeof(h2j_ctb), 256);
-    const size_t o_sl = align_up(o_slices + nslice * sizeof(h2j_slice), 256);
-    // H.264 K1 workgroup map: banded pictures first (their long chains start early), bands in order,
-    // then the others by transform-block count, most first (the dispatcher hands workgroups out in
-    // map order: the heaviest pictures start in the first round, not in the launch's tail)
-    // Banded pictures band-major (every picture's band 0, then every band 1, ...): a band waits on
-    // the band above, and picture-major order had each picture's lower bands holding workgroup
-    // slots while they waited (a batch of 4K H.264 pictures ran at a fraction of the GPU).  A band
-    // still follows the band above it in the map, so it never waits on one not yet dispatched.
-    std::vector<uint32_t> k1map;
-    {
-        int maxb = 0;
-        for (int k = 0; k < nf; k++)
-            if (s.frames[k].codec == H2J_CODEC_H264 && s.frames[k].k1bands > 1) maxb = std::max(maxb, static_cast<int>(s.frames[k].k1bands));
-        for (int bnd = 0; bnd < maxb; bnd++)
-            for (int k = 0; k < nf; k++) {
-                const h2j_frame& f = s.frames[k];
-                if (f.codec != H2J_CODEC_H264 || f.k1bands <= 1 || bnd >= static_cast<int>(f.k1bands)) continue;
-                k1map.push_back((static_cast<uint32_t>(k) << 8) | static_cast<uint32_t>(bnd));
-            }
-    }
-    // the same for h2j_k1_recon_h264's 8-wave workgroups: bands of 8 rows (16-row bands took two
-    // row rounds each, so a band below started a whole row time after the band above)
-    std::vector<uint32_t> k1map8;
-    {
-        int maxb = 0;
-        for (int k = 0; k < nf; k++)
-            if (s.frames[k].codec == H2J_CODEC_H264 && s.frames[k].k1bands > 1) maxb = std::max(maxb, (s.frames[k].ctb_h + 7) / 8);
-        for (int bnd = 0; bnd < maxb; bnd++)
-            for (int k = 0; k < nf; k++) {
-                const h2j_frame& f = s.frames[k];
-                if (f.codec != H2J_CODEC_H264 || f.k1bands <= 1 || bnd >= (f.ctb_h + 7) / 8) continue;
-                k1map8.push_back((static_cast<uint32_t>(k) << 8) | static_cast<uint32_t>(bnd));
-            }
-    }
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> un;
-        for (int k = 0; k < nf; k++) {
-            const h2j_frame& f = s.frames[k];
-            if (f.codec == H2J_CODEC_H264 && f.k1bands <= 1) un.emplace_back(f.ntu, static_cast<uint32_t>(k));
-        }
-        std::stable_sort(un.begin(), un.end(), [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) {
-                return a.first > b.first;
-            });
-        for (const auto& x : un) {
-            k1map.push_back(x.second << 8);
-            k1map8.push_back(x.second << 8);
-        }
-    }
-    // mixed-batch K1 map (h2j_k1_recon_any): every HEVC picture and H.264 band, tallest first so
-    // the longest chains start first; bands of one picture stay in order
-    std::vector<uint32_t> k1all;
-    {
-        std::vector<std::pair<int, uint32_t>> e;
-        for (int k = 0; k < nf; k++) {
-            const h2j_frame& f = s.frames[k];
-            if (f.codec != H2J_CODEC_HEVC) continue;
-            const int rows = f.ctb_h << (f.log2ctb - 4);  // in 16-sample rows
-            if (rows > kK1BandRows) {  // taller than 1088: a 16-wave workgroup per component group
-                e.emplace_back(-2000 - rows, (3u << 30) | (static_cast<uint32_t>(k) << 8) | 0u);
-                e.emplace_back(-2000 - rows, (3u << 30) | (static_cast<uint32_t>(k) << 8) | 1u);
-            } else {
-                e.emplace_back(-rows, (1u << 31) | (static_cast<uint32_t>(k) << 8));
-            }
-        }
-        for (uint32_t m : k1map) {
-            const h2j_frame& f = s.frames[m >> 8];
-            e.emplace_back(-std::min(f.ctb_h, 16) - (f.k1bands > 1 ? 1000 : 0), m);
-        }
-        std::stable_sort(e.begin(), e.end(),
-                         [](const std::pair<int, uint32_t>& a, const std::pair<int, uint32_t>& b) { return a.first < b.first; });
-        for (const auto& x : e) k1all.push_back(x.second);
-    }
-    std::vector<uint32_t> k1hevc;
-    for (uint32_t m : k1all)
-        if (m & 0x80000000u) k1hevc.push_back(m);
-    // K3 SAO map: the HEVC pictures with SAO, most CTBs first, cut into CTB-count classes (a picture
-    // joins the current class while it has more than half the class's CTBs; the last class takes
-    // the rest), one launch each, so no class pays for the largest picture's grid width
-    std::vector<uint32_t> saomap;
-    int sao_groups = 0, sao_first[H2J_SAO_GROUPS] = {}, sao_count[H2J_SAO_GROUPS] = {}, sao_ctbs[H2J_SAO_GROUPS] = {};
-    {
-        std::vector<std::pair<int, uint32_t>> e;
-        for (int k = 0; k < nf; k++) {
-            const h2j_frame& f = s.frames[k];
-            if (f.codec == H2J_CODEC_HEVC && f.pic2 != f.pic) e.emplace_back(f.ctb_w * f.ctb_h, static_cast<uint32_t>(k));
-        }
-        std::stable_sort(e.begin(), e.end(),
-                         [](const std::pair<int, uint32_t>& a, const std::pair<int, uint32_t>& b) { return a.first > b.first; });
-        for (size_t i = 0; i < e.size(); i++) {
-            const bool same = sao_groups > 0 && (sao_groups == H2J_SAO_GROUPS || 2 * e[i].first > sao_ctbs[sao_groups - 1]);
-            if (!same) {
-                sao_first[sao_groups] = static_cast<int>(i);
-                sao_ctbs[sao_groups] = e[i].first;
-                sao_groups++;
-            }
-            sao_count[sao_groups - 1]++;
-            saomap.push_back(e[i].second);
-        }
-    }
-    // K3s / K3r map: the scaled pictures by class (K3s: sample type x scale, K3r: sample type), one
-    // launch per class present, its grid as wide as the class's largest picture needs
-    // K3p map: a frame with two or more K3s levels among its views gets one h2j_pyramid instead of a K3s
-    // entry per level, by class (sample type, coarsest level)
-    std::vector<int> levels(static_cast<size_t>(nf), 0);  // per frame: mask of its K3s levels
-    int npyr = 0;
-    for (int v = 0; v < nv && nv > nf; v++)
-        if (s.scaled[v].scale_log2 >= 1 && s.scaled[v].scale_log2 <= 3) levels[s.scaled[v].frame] |= 1 << s.scaled[v].scale_log2;
-    for (int k = 0; k < nf; k++) {
-        if (levels[k] & (levels[k] - 1)) npyr++;
-        else levels[k] = 0;  // one level: K3s
-    }
-    std::vector<h2j_pyramid> pyrmap;
-    int py_first[H2J_PYR_CLASSES] = {}, py_count[H2J_PYR_CLASSES] = {}, py_tiles[H2J_PYR_CLASSES] = {};
-    for (int cls = 0; cls < H2J_PYR_CLASSES && npyr; cls++) {
-        py_first[cls] = static_cast<int>(pyrmap.size());
-        for (int k = 0; k < nf; k++) {
-            if (!levels[k]) continue;
-            const int kc = (levels[k] & 8) ? 3 : 2;
-            if (2 * (s.frames[k].bit_depth > 8 ? 1 : 0) + kc - 2 != cls) continue;
-            h2j_pyramid py{};
-            py.frame = k;
-            py.mask = levels[k];
-            for (int v = s.vfirst[k]; v < s.vfirst[k + 1]; v++)
-                if (s.scaled[v].scale_log2 >= 1 && s.scaled[v].scale_log2 <= 3) py.lvl[s.scaled[v].scale_log2 - 1] = s.scaled[v];
-            pyrmap.push_back(py);
-            py_count[cls]++;
-            py_tiles[cls] = std::max(py_tiles[cls], h2j_k3s_tiles(py.lvl[kc - 1].jpeg_w, py.lvl[kc - 1].jpeg_h));
-        }
-    }
-    std::vector<h2j_scaled> scalemap;
-    int sc_first[H2J_SCALE_CLASSES] = {}, sc_count[H2J_SCALE_CLASSES] = {}, sc_tiles[H2J_SCALE_CLASSES] = {};
-    for (int cls = 0; cls < H2J_SCALE_CLASSES && nscaled; cls++) {
-        sc_first[cls] = static_cast<int>(scalemap.size());
-        for (int k = 0; k < nv; k++) {
-            const h2j_scaled& sc = s.scaled[k];
-            if (sc.scale_log2 == 0 || (levels[sc.frame] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
-            const int hbd = s.frames[sc.frame].bit_depth > 8 ? 1 : 0;
-            const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
-            if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
-            scalemap.push_back(sc);
-            sc_count[cls]++;
-            sc_tiles[cls] = std::max(sc_tiles[cls], resample ? h2j_k3r_tiles(sc.jpeg_w, sc.jpeg_h) : h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
-        }
-    }
-    const size_t o_map = align_up(o_sl + nsl + 16, 256);
-    const size_t o_all = align_up(o_map + k1map.size() * 4 + 16, 256);
-    const size_t o_sao = align_up(o_all + k1all.size() * 4 + 16, 256);
-    const size_t o_map8 = align_up(o_sao + saomap.size() * 4 + 16, 256);
-    const size_t o_hev = align_up(o_map8 + k1map8.size() * 4 + 16, 256);
-    // scaled pictures present: the JPEG source views of all frames and the K3s / K3r map follow
-    const size_t o_jfr = align_up(o_hev + k1hevc.size() * 4 + 16, 256);
-    const bool views = nscaled || nv > nf;  // several renditions of a frame: a views array too
-    const size_t o_scl = views ? align_up(o_jfr + nv * sizeof(h2j_frame), 256) : o_jfr;
-    const size_t o_pyr = views ? align_up(o_scl + scalemap.size() * sizeof(h2j_scaled) + 16, 256) : o_jfr;
-    const size_t in_bytes = npyr ? align_up(o_pyr + pyrmap.size() * sizeof(h2j_pyramid) + 16, 256) : o_pyr;
-    if (!s.h_in.ensure(in_bytes)) return fail("pinned host allocation failed");
-    if (!s.d_in.ensure(in_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-    if (!s.d_arena.ensure(arena_bytes)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-    const int tiles = (max_mcu * 6 + 255) / 256;
-    const size_t seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(nv);
-    if (entropy) {
-        if (!s.d_seg.ensure(seg_cap)) return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-        if (!s.d_scratch.ensure(static_cast<size_t>(nv) * tiles * 4 + 256))
-            return fail(std::string("device allocation failed: ") + h2j_gpu_last_error());
-        if (!s.h_js.ensure(static_cast<size_t>(nv) * s.jstat_stride + 256)) return fail("pinned host allocation failed");
-    }
-    std::memcpy(s.h_in.p + o_frames, s.frames.data(), nf * sizeof(h2j_frame));
-    if (!k1map.empty()) std::memcpy(s.h_in.p + o_map, k1map.data(), k1map.size() * 4);
-    if (!k1all.empty()) std::memcpy(s.h_in.p + o_all, k1all.data(), k1all.size() * 4);
-    if (!saomap.empty()) std::memcpy(s.h_in.p + o_sao, saomap.data(), saomap.size() * 4);
-    if (!k1map8.empty()) std::memcpy(s.h_in.p + o_map8, k1map8.data(), k1map8.size() * 4);
-    if (!k1hevc.empty()) std::memcpy(s.h_in.p + o_hev, k1hevc.data(), k1hevc.size() * 4);
-    if (views) {
-        h2j_frame* jv = reinterpret_cast<h2j_frame*>(s.h_in.p + o_jfr);
-        for (int k = 0; k < nv; k++) jv[k] = jpeg_view(s.frames[s.scaled[k].frame], s.scaled[k], s.vjcoef[k]);
-        if (!scalemap.empty()) std::memcpy(s.h_in.p + o_scl, scalemap.data(), scalemap.size() * sizeof(h2j_scaled));
-        if (npyr) std::memcpy(s.h_in.p + o_pyr, pyrmap.data(), pyrmap.size() * sizeof(h2j_pyramid));
-    }
-    std::vector<size_t> bt(nf), bc(nf), bk(nf), bs(nf), bl(nf);
-    {
-        size_t a = 0, b = 0, c = 0, d = 0, e = 0;
-        for (int k = 0; k < nf; k++) {
-            const FrameJob& j = jobs[s.live[k]];
-            bt[k] = a; bc[k] = b; bk[k] = c; bs[k] = d; bl[k] = e;
-            a += j.tus.size(); b += j.coefs.size(); c += j.ctbs.size(); d += j.slices.size(); e += j.sl.size();
-        }
-    }
+int Engine::ensure_buffers(Slot& s) {
+    const ChunkPlan& p = s.plan;
+    const std::string dev_failed = "device allocation failed: ";
+    if (!s.h_in.ensure(p.at.bytes)) return fail("pinned host allocation failed");
+    if (!s.d_in.ensure(p.at.bytes)) return fail(dev_failed + h2j_gpu_last_error());
+    if (!s.d_arena.ensure(p.arena_bytes)) return fail(dev_failed + h2j_gpu_last_error());
+    if (!s.entropy) return 0;
+    if (!s.d_seg.ensure(p.seg_cap)) return fail(dev_failed + h2j_gpu_last_error());
+    if (!s.d_scratch.ensure(static_cast<size_t>(p.nv) * p.tiles * 4 + 256)) return fail(dev_failed + h2j_gpu_last_error());
+    if (!s.h_js.ensure(static_cast<size_t>(p.nv) * p.jstat_stride + 256)) return fail("pinned host allocation failed");
+    return 0;
+}
+
+// the chunk's upload: frames, maps, views and the jobs' records at their places (plan.at) in the pinned buffer
+void Engine::pack_staging(Slot& s, bool pool_free) {
+    const ChunkPlan& p = s.plan;
     uint8_t* hin = s.h_in.p;
-    auto pack = [&](int k) {
+    auto put = [&](size_t at, const void* src, size_t bytes) {
+        if (bytes) std::memcpy(hin + at, src, bytes);
+    };
+    put(p.at.frames, p.frames.data(), p.nf * sizeof(h2j_frame));
+    put(p.at.k1map, p.k1map.data(), p.k1map.size() * 4);
+    put(p.at.k1all, p.k1all.data(), p.k1all.size() * 4);
+    put(p.at.sao, p.saomap.data(), p.saomap.size() * 4);
+    put(p.at.k1map8, p.k1map8.data(), p.k1map8.size() * 4);
+    put(p.at.k1hevc, p.k1hevc.data(), p.k1hevc.size() * 4);
+    if (p.views) {
+        h2j_frame* jv = reinterpret_cast<h2j_frame*>(hin + p.at.jframes);
+        for (int v = 0; v < p.nv; v++) jv[v] = p.view(v);
+        put(p.at.scale, p.scalemap.data(), p.scalemap.size() * sizeof(h2j_scaled));
+        put(p.at.pyr, p.pyrmap.data(), p.pyrmap.size() * sizeof(h2j_pyramid));
+    }
+    const std::vector<FrameJob>& jobs = *s.jobs;
+    auto pack = [&](int k) {  // the frame's record ranges are where plan_chunk numbered them
         const FrameJob& j = jobs[s.live[k]];
-        if (!j.tus.empty()) std::memcpy(hin + o_tus + bt[k] * sizeof(h2j_tu), j.tus.data(), j.tus.size() * sizeof(h2j_tu));
-        if (!j.coefs.empty()) std::memcpy(hin + o_coefs + bc[k] * sizeof(h2j_coef), j.coefs.data(), j.coefs.size() * sizeof(h2j_coef));
-        if (!j.ctbs.empty()) std::memcpy(hin + o_ctbs + bk[k] * sizeof(h2j_ctb), j.ctbs.data(), j.ctbs.size() * sizeof(h2j_ctb));
-        if (!j.slices.empty()) std::memcpy(hin + o_slices + bs[k] * sizeof(h2j_slice), j.slices.data(), j.slices.size() * sizeof(h2j_slice));
-        if (!j.sl.empty()) std::memcpy(hin + o_sl + bl[k], j.sl.data(), j.sl.size());
+        const h2j_frame& f = p.frames[k];
+        put(p.at.tus + f.tu * sizeof(h2j_tu), j.tus.data(), j.tus.size() * sizeof(h2j_tu));
+        put(p.at.coefs + f.coef * sizeof(h2j_coef), j.coefs.data(), j.coefs.size() * sizeof(h2j_coef));
+        put(p.at.ctbs + f.ctb * sizeof(h2j_ctb), j.ctbs.data(), j.ctbs.size() * sizeof(h2j_ctb));
+        put(p.at.slices + f.slice * sizeof(h2j_slice), j.slices.data(), j.slices.size() * sizeof(h2j_slice));
+        put(p.at.sl + f.sl, j.sl.data(), j.sl.size());
     };
     const double tp = now_ms();
-    if (pool_free) par(nf, pack);
-    else for (int k = 0; k < nf; k++) pack(k);
+    if (pool_free) par(p.nf, pack);
+    else for (int k = 0; k < p.nf; k++) pack(k);
     stats[ST_PACK] += now_ms() - tp;
-    uint8_t* din = static_cast<uint8_t*>(s.d_in.p);
+}
+
+// the plan's descriptor with the device pointers of this slot's buffers
+void Engine::fill_descriptors(Slot& s) {
+    const ChunkPlan& p = s.plan;
+    const uint8_t* din = static_cast<const uint8_t*>(s.d_in.p);
+    uint8_t* scratch = static_cast<uint8_t*>(s.d_scratch.p);
     h2j_gpu_batch& b = s.batch;
-    b.nframes = nf;
-    b.max_w = max_w;
-    b.max_h = max_h;
-    b.max_mcu = max_mcu;
-    b.max_ntu = max_ntu;
-    b.max_ctbs = max_ctbs;
-    b.has_hevc = 0;
-    b.has_h264 = 0;
-    b.has_mbaff = 0;
-    b.h264_pels = 0;
-    for (int k = 0; k < nf; k++) {
-        const h2j_frame& fk = s.frames[k];
-        if (fk.codec == H2J_CODEC_HEVC) b.has_hevc = 1;
-        if (fk.codec != H2J_CODEC_H264) continue;
-        b.has_h264 = 1;
-        if (fk.mbaff) b.has_mbaff = 1;
-        else b.h264_pels |= fk.bit_depth == 8 ? 1 : 2;
-    }
-    b.frames = reinterpret_cast<const h2j_frame*>(din + o_frames);
-    b.tus = reinterpret_cast<const h2j_tu*>(din + o_tus);
-    b.coefs = reinterpret_cast<const h2j_coef*>(din + o_coefs);
-    b.ctbs = reinterpret_cast<const h2j_ctb*>(din + o_ctbs);
-    b.slices = reinterpret_cast<const h2j_slice*>(din + o_slices);
-    b.sl = din + o_sl;
-    b.k1map = reinterpret_cast<const uint32_t*>(din + o_map);
-    b.k1wgs = static_cast<int32_t>(k1map.size());
-    b.k1all = reinterpret_cast<const uint32_t*>(din + o_all);
-    b.k1all_n = static_cast<int32_t>(k1all.size());
-    b.k1map8 = reinterpret_cast<const uint32_t*>(din + o_map8);
-    b.k1wgs8 = static_cast<int32_t>(k1map8.size());
-    b.k1hevc = reinterpret_cast<const uint32_t*>(din + o_hev);
-    b.k1hevc_n = static_cast<int32_t>(k1hevc.size());
-    b.sao_map = reinterpret_cast<const uint32_t*>(din + o_sao);
-    b.sao_groups = sao_groups;
-    for (int g = 0; g < H2J_SAO_GROUPS; g++) {
-        b.sao_first[g] = sao_first[g];
-        b.sao_count[g] = sao_count[g];
-        b.sao_ctbs[g] = sao_ctbs[g];
-    }
-    b.jframes = views ? reinterpret_cast<const h2j_frame*>(din + o_jfr) : b.frames;
-    b.scale_map = !scalemap.empty() ? reinterpret_cast<const h2j_scaled*>(din + o_scl) : nullptr;
-    b.pyr_map = npyr ? reinterpret_cast<const h2j_pyramid*>(din + o_pyr) : nullptr;
-    for (int c = 0; c < H2J_PYR_CLASSES; c++) {
-        b.pyr_first[c] = py_first[c];
-        b.pyr_count[c] = py_count[c];
-        b.pyr_tiles[c] = py_tiles[c];
-    }
-    for (int c = 0; c < H2J_SCALE_CLASSES; c++) {
-        b.scale_first[c] = sc_first[c];
-        b.scale_count[c] = sc_count[c];
-        b.scale_tiles[c] = sc_tiles[c];
-    }
-    b.hevc_pels = 0;
-    for (int k = 0; k < nf; k++)
-        if (s.frames[k].codec == H2J_CODEC_HEVC) b.hevc_pels |= (s.frames[k].bit_depth > 8 || s.frames[k].bit_depth_c > 8) ? 2 : 1;
+    b = p.desc;
+    b.frames = reinterpret_cast<const h2j_frame*>(din + p.at.frames);
+    b.tus = reinterpret_cast<const h2j_tu*>(din + p.at.tus);
+    b.coefs = reinterpret_cast<const h2j_coef*>(din + p.at.coefs);
+    b.ctbs = reinterpret_cast<const h2j_ctb*>(din + p.at.ctbs);
+    b.slices = reinterpret_cast<const h2j_slice*>(din + p.at.slices);
+    b.sl = din + p.at.sl;
+    b.k1map = reinterpret_cast<const uint32_t*>(din + p.at.k1map);
+    b.k1all = reinterpret_cast<const uint32_t*>(din + p.at.k1all);
+    b.k1map8 = reinterpret_cast<const uint32_t*>(din + p.at.k1map8);
+    b.k1hevc = reinterpret_cast<const uint32_t*>(din + p.at.k1hevc);
+    b.sao_map = reinterpret_cast<const uint32_t*>(din + p.at.sao);
+    b.jframes = p.views ? reinterpret_cast<const h2j_frame*>(din + p.at.jframes) : b.frames;
+    b.scale_map = !p.scalemap.empty() ? reinterpret_cast<const h2j_scaled*>(din + p.at.scale) : nullptr;
+    b.pyr_map = !p.pyrmap.empty() ? reinterpret_cast<const h2j_pyramid*>(din + p.at.pyr) : nullptr;
     b.arena = static_cast<uint8_t*>(s.d_arena.p);
-    b.jpeg_dense = entropy ? 0 : 1;
-    {  // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
-        int k4a = 0;
-        // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
-        for (int k = 0; k < nv; k++) k4a += (h2j_sao_folds_variance(s.frames[s.scaled[k].frame]) && s.scaled[k].scale_log2 == 0) ? 0 : 1;
-        b.k4a_frames = k4a;
-    }
-    b.seg = entropy ? static_cast<uint8_t*>(s.d_seg.p) : nullptr;
-    b.seg_cap = entropy ? seg_cap : 0;
-    b.seg_total = entropy ? static_cast<uint64_t*>(s.d_scratch.p) : nullptr;
-    b.tile_bits = entropy ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(s.d_scratch.p) + 256) : nullptr;
+    b.jpeg_dense = s.entropy ? 0 : 1;
+    b.seg = s.entropy ? static_cast<uint8_t*>(s.d_seg.p) : nullptr;
+    b.seg_cap = s.entropy ? p.seg_cap : 0;
+    b.seg_total = s.entropy ? reinterpret_cast<uint64_t*>(scratch) : nullptr;
+    b.tile_bits = s.entropy ? reinterpret_cast<uint32_t*>(scratch + 256) : nullptr;
     // K4 / K5 read only the views and the arena: with several renditions of a frame they run on a
     // descriptor whose frames are the nv views (nv == nf: the one descriptor, as without renditions)
     h2j_gpu_batch& jb = s.jbatch;
     jb = b;
-    if (nv > nf) {
-        jb.nframes = nv;
+    if (p.nv > p.nf) {
+        jb.nframes = p.nv;
         jb.frames = jb.jframes = b.jframes;
     }
+}
+
+// upload, the kernels of s.stages, and the stats download, on the slot's stream
+int Engine::launch(Slot& s, const Slot* after) {
+    const ChunkPlan& p = s.plan;
+    const h2j_gpu_batch& b = s.batch;
+    const h2j_gpu_batch& jb = s.jbatch;
     void* st = s.stream;
     int r = 0;
-    r |= h2j_gpu_event_record(s.ev[0], st);
-    r |= h2j_gpu_memcpy_h2d(din, hin, in_bytes, st);
-    r |= h2j_gpu_event_record(s.ev[12], st);
-    stats[ST_H2D_BYTES] += static_cast<double>(in_bytes);
+    r |= h2j_gpu_event_record(s.ev[EV_BEGIN], st);
+    r |= h2j_gpu_memcpy_h2d(s.d_in.p, s.h_in.p, p.at.bytes, st);
+    r |= h2j_gpu_event_record(s.ev[EV_H2D], st);
+    stats[ST_H2D_BYTES] += static_cast<double>(p.at.bytes);
     // two GPU sub-chunks of one parsed range (4K batches, mixed batches past the slot's HBM budget)
     // would otherwise run their kernels side by side: the GPU is not the bound (the host entropy
     // threads are), and concurrent launches inflated every stage's event time and rocprof duration
     // (r05: 4K K4b 1.14 ms and the arena fill 1.18 ms per 256 pictures, 0.004 / 0.037 ms alone)
-    if (after && after->pending) r |= h2j_gpu_stream_wait_event(st, after->ev[6]);
-    r |= h2j_gpu_event_record(s.ev[13], st);
-    r |= h2j_gpu_memset(s.d_arena.p, 0, s.zero_bytes, st);
-    r |= h2j_gpu_event_record(s.ev[1], st);
+    if (after && after->pending) r |= h2j_gpu_stream_wait_event(st, after->ev[EV_K5]);
+    r |= h2j_gpu_event_record(s.ev[EV_GPU_BEGIN], st);
+    r |= h2j_gpu_memset(s.d_arena.p, 0, p.zero_bytes, st);
+    r |= h2j_gpu_event_record(s.ev[EV_ZEROED], st);
     if (r) return drain_fail(s, std::string("upload failed: ") + h2j_gpu_last_error());
     if (h2j_gpu_prep(&b, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[8], st);
+    h2j_gpu_event_record(s.ev[EV_K0], st);
     if (h2j_gpu_predict(&b, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[2], st);
-    if (stages >= 2 && h2j_gpu_deblock(&b, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[3], st);
-    if (stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[4], st);
-    if (stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
-    h2j_gpu_event_record(s.ev[16], st);
-    if (stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[5], st);
-    if (entropy && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
-    h2j_gpu_event_record(s.ev[6], st);
-    if (entropy) {
+    h2j_gpu_event_record(s.ev[EV_K1], st);
+    if (s.stages >= 2 && h2j_gpu_deblock(&b, st)) return drain_fail(s, h2j_gpu_last_error());
+    h2j_gpu_event_record(s.ev[EV_K2], st);
+    if (s.stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
+    h2j_gpu_event_record(s.ev[EV_K3], st);
+    if (s.stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
+    h2j_gpu_event_record(s.ev[EV_SCALE], st);
+    if (s.stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    h2j_gpu_event_record(s.ev[EV_K4], st);
+    if (s.entropy && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    h2j_gpu_event_record(s.ev[EV_K5], st);
+    if (s.entropy) {
         r |= h2j_gpu_memcpy_d2h(s.h_js.p, s.d_scratch.p, 8, st);  // seg_total
-        r |= h2j_gpu_memcpy_d2h(s.h_js.p + 256, static_cast<uint8_t*>(s.d_arena.p) + s.jstat_base,
-                                static_cast<size_t>(nv) * s.jstat_stride, st);
+        r |= h2j_gpu_memcpy_d2h(s.h_js.p + 256, static_cast<uint8_t*>(s.d_arena.p) + p.jstat_base,
+                                static_cast<size_t>(p.nv) * p.jstat_stride, st);
         if (r) return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
     }
-    h2j_gpu_event_record(s.ev[9], st);
-    // the payloads follow in the same stream, sized by the pinned buffer (1.25x the largest total
-    // seen): no host round trip between the kernels and the copy.  r04/r05 enqueued the copy in
-    // sync() once the host had read the total: at 4K its interval measured 40-78 ms per step for
-    // 121 MB against 4 ms for the bare copy (tools/d2h_probe: 30 GB/s pinned) -- the submitting
-    // driver thread waited for CPU behind the 16 entropy threads (profiles/r05_4k_d2h.md).  A
-    // total above the capacity (first chunks, growth) is copied again whole in sync().
+    h2j_gpu_event_record(s.ev[EV_STATS], st);
+    return 0;
+}
+
+// the payloads follow in the same stream, sized by the pinned buffer (1.25x the largest total
+// seen): no host round trip between the kernels and the copy.  r04/r05 enqueued the copy in
+// sync() once the host had read the total: at 4K its interval measured 40-78 ms per step for
+// 121 MB against 4 ms for the bare copy (tools/d2h_probe: 30 GB/s pinned) -- the submitting
+// driver thread waited for CPU behind the 16 entropy threads (profiles/r05_4k_d2h.md).  A
+// total above the capacity (first chunks, growth) is copied again whole in sync().
+int Engine::enqueue_payload_copy(Slot& s) {
     if (s.small_runs >= 8) {  // the slot's last chunk has been assembled: h_seg is free to go
         const double tg = now_ms();
         const size_t keep = s.small_max + s.small_max / 4 + 16;
@@ -969,26 +598,34 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
         s.small_runs = 0;
     }
     s.pay_pre = 0;
-    s.px = 0;
-    for (int k = 0; k < nv; k++) s.px += static_cast<double>(s.scaled[k].jpeg_w) * s.scaled[k].jpeg_h;  // JPEG pixels
-    if (entropy && s.h_seg.cap > 0) {
+    if (s.entropy && s.h_seg.cap > 0) {
         // the copy is sized by the engine's payload-per-pixel estimate (1.3x, 4 KB
         // granules), not by the buffer's high-water mark: a small chunk after a 4K one moves its own
         // few MB, not the 4K chunk's 150 MB
-        size_t want = seg_cap;
-        if (pay_per_px > 0) want = (static_cast<size_t>(1.3 * pay_per_px * s.px) + 65536 + 4095) & ~static_cast<size_t>(4095);
-        s.pay_pre = std::min(std::min(s.h_seg.cap, seg_cap), want);
-        h2j_gpu_event_record(s.ev[10], st);
-        if (h2j_gpu_memcpy_d2h(s.h_seg.p, s.d_seg.p, s.pay_pre, st))
+        size_t want = s.plan.seg_cap;
+        if (pay_per_px > 0) want = (static_cast<size_t>(1.3 * pay_per_px * s.plan.px) + 65536 + 4095) & ~static_cast<size_t>(4095);
+        s.pay_pre = std::min(std::min(s.h_seg.cap, s.plan.seg_cap), want);
+        h2j_gpu_event_record(s.ev[EV_PAY_BEGIN], s.stream);
+        if (h2j_gpu_memcpy_d2h(s.h_seg.p, s.d_seg.p, s.pay_pre, s.stream))
             return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
-        h2j_gpu_event_record(s.ev[11], st);
+        h2j_gpu_event_record(s.ev[EV_PAY_END], s.stream);
     }
+    return 0;
+}
+
+int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slot* after) {
+    s.stages = stages;
+    s.entropy = entropy;
+    s.pending = false;
+    if (s.live.empty()) return 0;
+    plan_chunk(*s.jobs, s.live, s.plan);
+    if (ensure_buffers(s)) return -1;
+    pack_staging(s, pool_free);
+    fill_descriptors(s);
+    if (launch(s, after) || enqueue_payload_copy(s)) return -1;
     s.pending = true;
     double bytes = 0;
-    for (int k = 0; k < nf; k++) {
-        const double S = 1.5 * s.frames[k].out_w * s.frames[k].out_h;
-        bytes += S * (4.0 + (s.frames[k].bit_depth > 8 ? 2.0 : 1.0));
-    }
+    for (const h2j_frame& f : s.plan.frames) bytes += 1.5 * f.out_w * f.out_h * (4.0 + (f.bit_depth > 8 ? 2.0 : 1.0));
     stats[ST_BYTES] += bytes;
     return 0;
 }
@@ -1002,8 +639,8 @@ int Engine::sync(Slot& s) {
         uint64_t total = 0;
         std::memcpy(&total, s.h_js.p, 8);
         stats[ST_PAY_BYTES] += static_cast<double>(total);
-        if (s.px > 0) {  // payload per pixel: a running mean, never below the last chunk's
-            const double ratio = static_cast<double>(total) / s.px;
+        if (s.plan.px > 0) {  // payload per pixel: a running mean, never below the last chunk's
+            const double ratio = static_cast<double>(total) / s.plan.px;
             pay_per_px = pay_per_px > 0 ? std::max(ratio, 0.7 * pay_per_px + 0.3 * ratio) : ratio;
         }
         stats[ST_PAY_COPIED] += static_cast<double>(s.pay_pre);  // the in-stream copy, used or not
@@ -1013,10 +650,10 @@ int Engine::sync(Slot& s) {
             stats[ST_HOST_GROW] += now_ms() - tg;
             stats[ST_PAY_COPIED] += static_cast<double>(total);
             pay_late = true;
-            h2j_gpu_event_record(s.ev[14], s.stream);
+            h2j_gpu_event_record(s.ev[EV_PAY2_BEGIN], s.stream);
             if (h2j_gpu_memcpy_d2h(s.h_seg.p, s.d_seg.p, total, s.stream))
                 return fail(std::string("download failed: ") + h2j_gpu_last_error());
-            h2j_gpu_event_record(s.ev[15], s.stream);
+            h2j_gpu_event_record(s.ev[EV_PAY2_END], s.stream);
         }
         // the pinned buffer shrinks after 8 chunks in a row that used less than a quarter of it
         if (total * 4 < s.h_seg.cap) {
@@ -1026,31 +663,31 @@ int Engine::sync(Slot& s) {
             s.small_runs = 0;
         }
     }
-    if (h2j_gpu_event_record(s.ev[7], s.stream) || h2j_gpu_stream_sync(s.stream))
+    if (h2j_gpu_event_record(s.ev[EV_END], s.stream) || h2j_gpu_stream_sync(s.stream))
         return fail(std::string("download failed: ") + h2j_gpu_last_error());
     // the H2D copy alone; the arena fill (after any wait for the other slot's kernels) counts with K0
-    stats[ST_H2D] += h2j_gpu_event_elapsed_ms(s.ev[0], s.ev[12]);
-    stats[ST_PREP] += h2j_gpu_event_elapsed_ms(s.ev[13], s.ev[8]);
-    stats[ST_RECON] += h2j_gpu_event_elapsed_ms(s.ev[8], s.ev[2]);
+    stats[ST_H2D] += h2j_gpu_event_elapsed_ms(s.ev[EV_BEGIN], s.ev[EV_H2D]);
+    stats[ST_PREP] += h2j_gpu_event_elapsed_ms(s.ev[EV_GPU_BEGIN], s.ev[EV_K0]);
+    stats[ST_RECON] += h2j_gpu_event_elapsed_ms(s.ev[EV_K0], s.ev[EV_K1]);
     stats[ST_CHUNKS] += 1;
-    stats[ST_DEBLOCK] += h2j_gpu_event_elapsed_ms(s.ev[2], s.ev[3]);
-    stats[ST_SAO] += h2j_gpu_event_elapsed_ms(s.ev[3], s.ev[4]);
-    stats[ST_SCALE] += h2j_gpu_event_elapsed_ms(s.ev[4], s.ev[16]);
-    stats[ST_JPEG] += h2j_gpu_event_elapsed_ms(s.ev[16], s.ev[5]);
-    stats[ST_ENTROPY] += h2j_gpu_event_elapsed_ms(s.ev[5], s.ev[6]);
+    stats[ST_DEBLOCK] += h2j_gpu_event_elapsed_ms(s.ev[EV_K1], s.ev[EV_K2]);
+    stats[ST_SAO] += h2j_gpu_event_elapsed_ms(s.ev[EV_K2], s.ev[EV_K3]);
+    stats[ST_SCALE] += h2j_gpu_event_elapsed_ms(s.ev[EV_K3], s.ev[EV_SCALE]);
+    stats[ST_JPEG] += h2j_gpu_event_elapsed_ms(s.ev[EV_SCALE], s.ev[EV_K4]);
+    stats[ST_ENTROPY] += h2j_gpu_event_elapsed_ms(s.ev[EV_K4], s.ev[EV_K5]);
     // copies only (the payload copy is enqueued once the host has read the sizes)
-    const double d2h_stats = h2j_gpu_event_elapsed_ms(s.ev[6], s.ev[9]);
+    const double d2h_stats = h2j_gpu_event_elapsed_ms(s.ev[EV_K5], s.ev[EV_STATS]);
     // both payload copies when the in-stream one fell short (the second one's events had
     // overwritten the first's)
-    const double d2h_pay = (s.entropy && s.pay_pre ? h2j_gpu_event_elapsed_ms(s.ev[10], s.ev[11]) : 0.0) +
-                           (pay_late ? h2j_gpu_event_elapsed_ms(s.ev[14], s.ev[15]) : 0.0);
+    const double d2h_pay = (s.entropy && s.pay_pre ? h2j_gpu_event_elapsed_ms(s.ev[EV_PAY_BEGIN], s.ev[EV_PAY_END]) : 0.0) +
+                           (pay_late ? h2j_gpu_event_elapsed_ms(s.ev[EV_PAY2_BEGIN], s.ev[EV_PAY2_END]) : 0.0);
     stats[ST_D2H] += d2h_stats + d2h_pay;
     stats[ST_D2H_STATS] += d2h_stats;
     stats[ST_D2H_PAY] += d2h_pay;
     ChunkTime ct;
     ct.frames = static_cast<int>(s.live.size());
-    ct.k1_ms = h2j_gpu_event_elapsed_ms(s.ev[8], s.ev[2]);
-    ct.kernels_ms = h2j_gpu_event_elapsed_ms(s.ev[13], s.ev[6]);
+    ct.k1_ms = h2j_gpu_event_elapsed_ms(s.ev[EV_K0], s.ev[EV_K1]);
+    ct.kernels_ms = h2j_gpu_event_elapsed_ms(s.ev[EV_GPU_BEGIN], s.ev[EV_K5]);
     chunk_log.push_back(ct);
     return 0;
 }
@@ -1059,7 +696,7 @@ int Engine::sync(Slot& s) {
 // workgroup per picture), small enough that parse / GPU / assembly overlap;
 // the last quarter is split into shrinking chunks so that the GPU work left
 // after the last picture is parsed (the pipeline's tail) is short.
-std::vector<int> chunk_plan(int n) {
+std::vector<int> chunk_bounds(int n) {
     int chunk = n >= 512 ? 256 : n;
     const char* e = std::getenv("H2J_CHUNK");
     if (e && std::atoi(e) > 0) chunk = std::atoi(e);
@@ -1084,7 +721,7 @@ std::vector<int> chunk_plan(int n) {
 // Throughput plan (asynchronous batches): one parse chunk of up to 1024 pictures (K1 runs up to
 // four pictures per workgroup on launches that large); the GPU tail of a batch is hidden behind
 // the next batch's entropy decoding instead of being cut into shrinking chunks.
-std::vector<int> chunk_plan_throughput(int n) {
+std::vector<int> chunk_bounds_throughput(int n) {
     int chunk = 1024;
     const char* e = std::getenv("H2J_CHUNK_ASYNC");
     if (e && std::atoi(e) > 0) chunk = std::atoi(e);
@@ -1102,14 +739,13 @@ static double hbm_estimate(const FrameJob& j) {
     const double px = static_cast<double>(j.hdr.width) * j.hdr.height;
     // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample, a resized picture's 1.5 W_o H_o B; its
     // JPEG regions shrink by more)
-    const int k0 = j.outs.empty() ? j.scale_log2 : j.outs[0].scale_log2;  // the first (or only) output
-    const int fw0 = j.outs.empty() ? j.fit_w : j.outs[0].fit_w, fh0 = j.outs.empty() ? j.fit_h : j.outs[0].fit_h;
-    const double spic = k0 == H2J_SCALE_RESAMPLE ? 1.5 * fw0 * fh0 : k0 ? 1.5 * px / (1 << 2 * k0) : 0.0;
+    const FrameJob::Output o0 = j.nouts ? j.outs[0] : FrameJob::Output();  // the first output (none: a failed job)
+    const double spic = o0.scale_log2 == H2J_SCALE_RESAMPLE ? 1.5 * o0.fit_w * o0.fit_h : o0.scale_log2 ? 1.5 * px / (1 << 2 * o0.scale_log2) : 0.0;
     double est = px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + spic + (1 << 20);
     // several renditions: each output beyond the first adds its 8-bit planes (1.5 B per output sample), its
     // jcoef / tile region and its share of the payload pool (272 B per 8x8 block each: 6.4 B per sample),
     // and its jstat and tile_bits (a few KB)
-    for (size_t r = 1; r < j.outs.size(); r++) {
+    for (int r = 1; r < j.nouts; r++) {
         const FrameJob::Output& o = j.outs[r];
         if (o.error) continue;
         const double opx = o.scale_log2 == H2J_SCALE_RESAMPLE ? static_cast<double>(o.fit_w) * o.fit_h
@@ -1119,7 +755,7 @@ static double hbm_estimate(const FrameJob& j) {
     return est;
 }
 // JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
-static int views_estimate(const FrameJob& j) { return std::max<int>(1, static_cast<int>(j.outs.size())); }
+static int views_estimate(const FrameJob& j) { return std::max(1, j.nouts); }
 
 void Engine::start_threads() {
     std::lock_guard<std::mutex> g(amu);
@@ -1159,15 +795,10 @@ void Engine::parse_loop() {
             pool->parallel_for(b->n, [&](int k) {
                 const int i = order[static_cast<size_t>(k)];
                 jobs[i].threads = slice_threads;
-                if (b->rbase.empty()) {
-                    parse_item(b->data[i], b->sizes[i], b->opts.empty() ? h2j_out_opts2{} : b->opts[static_cast<size_t>(i)], jobs[i]);
-                    if (jobs[i].error != H2J_ERR_OUT_OPTS) b->nparsed.fetch_add(1, std::memory_order_relaxed);
-                } else {
-                    bool ran = false;
-                    parse_item_multi(b->data[i], b->sizes[i], b->opts.data() + b->rbase[i], b->rbase[i + 1] - b->rbase[i], jobs[i], &ran);
-                    if (ran) b->nparsed.fetch_add(1, std::memory_order_relaxed);
-                }
-                jobs[i].out_base = b->rbase.empty() ? i : b->rbase[i];
+                bool ran = false;
+                parse_item_multi(b->data[i], b->sizes[i], b->opts.data() + b->rbase[i], b->rbase[i + 1] - b->rbase[i], jobs[i], &ran);
+                if (ran) b->nparsed.fetch_add(1, std::memory_order_relaxed);
+                jobs[i].out_base = b->rbase[i];
                 if (b->left[b->chunk_of[i]].fetch_sub(1) == 1) {
                     std::lock_guard<std::mutex> g2(amu);
                     acv.notify_all();
@@ -1207,8 +838,7 @@ void Engine::drive_loop() {
         b->msg.assign(static_cast<size_t>(b->nout), std::string());
         if (jobs)
             for (int i = 0; i < b->n; i++) {
-                const int o0 = b->rbase.empty() ? i : b->rbase[i], o1 = b->rbase.empty() ? i + 1 : b->rbase[i + 1];
-                for (int o = o0; o < o1; o++) {
+                for (int o = b->rbase[i]; o < b->rbase[i + 1]; o++) {
                     if (b->status[o] == 0) continue;
                     if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
                     else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)]);
@@ -1236,12 +866,12 @@ int Engine::run_batch(Batch& b) {
     auto assemble = [&](Slot& s) -> int {
         if (sync(s)) return -2;
         const double ta = now_ms();
-        const int nf = static_cast<int>(s.live.size()), nv = static_cast<int>(s.scaled.size());
-        const int nr = static_cast<int>(s.rends.size());
+        const ChunkPlan& p = s.plan;
+        const int nf = p.nf, nv = p.nv, nr = static_cast<int>(p.rends.size());
         const uint8_t* js = s.h_js.p + 256;
         std::vector<size_t> sz(nv);  // per view: its JPEG, encoded once
         auto size_of = [&](int k) {
-            const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
+            const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * p.jstat_stride);
             sz[k] = st->seg_off == ~0ull ? 0 : jpeg_container_size(*st, s.h_seg.p + st->seg_off, kLavcIdent);
         };
         par(nv, size_of);
@@ -1250,9 +880,9 @@ int Engine::run_batch(Batch& b) {
         std::vector<size_t> at(nr);
         std::vector<int> first(nv, -1);  // per view: its first rendition with a place
         for (int q = 0; q < nr; q++) {
-            const int i = s.rends[q].out, k = s.rends[q].view;
+            const int i = p.rends[q].out, k = p.rends[q].view;
             // a device-side failure (e.g. a K1 band hand-off timed out) is recorded in the frame's own jstat
-            const h2j_jstat* stf = reinterpret_cast<const h2j_jstat*>(js + s.vfirst[s.scaled[k].frame] * s.jstat_stride);
+            const h2j_jstat* stf = reinterpret_cast<const h2j_jstat*>(js + p.vfirst[p.scaled[k].frame] * p.jstat_stride);
             at[q] = ~static_cast<size_t>(0);
             if (stf->dev_error) {
                 status[i] = -52;
@@ -1277,14 +907,14 @@ int Engine::run_batch(Batch& b) {
         }
         auto write = [&](int k) {
             if (first[k] < 0) return;
-            const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * s.jstat_stride);
-            const h2j_scaled& sc = s.scaled[k];
+            const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * p.jstat_stride);
+            const h2j_scaled& sc = p.scaled[k];
             jpeg_write_container(*st, s.h_seg.p + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[first[k]]);
         };
         par(nv, write);
         if (nr > nv)
             for (int q = 0; q < nr; q++) {
-                const int k = s.rends[q].view;
+                const int k = p.rends[q].view;
                 if (at[q] != ~static_cast<size_t>(0) && first[k] != q) std::memcpy(b.out + at[q], b.out + at[first[k]], sz[k]);
             }
         stats[ST_ASSEMBLE] += now_ms() - ta;
@@ -1340,12 +970,9 @@ int Engine::run_batch(Batch& b) {
                     jobs[k].error = -3;
                     jobs[k].message = "field picture (PAFF): no frame from one field (H2J_STRICT_REFERENCE)";
                 }
-                if (b.rbase.empty()) {
-                    status[k] = jobs[k].error;
-                } else {  // a failed item fails every rendition; else each rendition's own options decide
-                    for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++)
-                        status[o] = jobs[k].error ? jobs[k].error : jobs[k].outs[static_cast<size_t>(o - b.rbase[k])].error;
-                }
+                // a failed item fails every rendition; else each rendition's own options decide
+                for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++)
+                    status[o] = jobs[k].error ? jobs[k].error : jobs[k].outs[o - b.rbase[k]].error;
                 if (jobs[k].error == 0) s.live.push_back(k);
             }
             Slot& prev = slot[(sc + 1) & 1];
@@ -1424,10 +1051,12 @@ void h2j_engine_destroy(h2j_engine* e) { delete e; }
 
 const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no engine"; }
 
-// submit one batch; latency: the synchronous plan (small tail chunks), else the throughput plan
-static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
-                            const h2j_out_opts* opts, const h2j_out_opts2* opts2, uint8_t* out, size_t out_cap,
-                            size_t* out_off, size_t* out_len, int* status, bool latency, const int32_t* nrend = nullptr) {
+// submit one batch; latency: the synchronous plan (small tail chunks), else the throughput plan.
+// Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
+// them (opts null: the decoded size)
+static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                            const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
     b->n = n;
@@ -1438,21 +1067,17 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     b->out_off = out_off;
     b->out_len = out_len;
     b->status = status;
-    b->nout = n;
-    if (nrend) {  // several renditions per item: opts2 and the output arrays are item-major over all of them
-        b->rbase.assign(static_cast<size_t>(n) + 1, 0);
-        for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + nrend[i];
-        b->nout = b->rbase[n];
-    }
-    if (opts2) b->opts.assign(opts2, opts2 + b->nout);
-    else if (opts)
-        for (int i = 0; i < n; i++) b->opts.push_back(h2j::opts2_of(opts[i]));
+    b->rbase.assign(static_cast<size_t>(n) + 1, 0);
+    for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + (nrend ? nrend[i] : 1);
+    b->nout = b->rbase[n];
+    if (opts) b->opts.assign(opts, opts + b->nout);
+    else b->opts.assign(static_cast<size_t>(b->nout), h2j::kPlainOutput);
     for (int i = 0; i < b->nout; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
         status[i] = 0;
     }
-    b->bounds = latency ? h2j::chunk_plan(n) : h2j::chunk_plan_throughput(n);
+    b->bounds = latency ? h2j::chunk_bounds(n) : h2j::chunk_bounds_throughput(n);
     const int nchunks = static_cast<int>(b->bounds.size()) - 1;
     b->chunk_of.assign(static_cast<size_t>(n), 0);
     for (int c = 0; c < nchunks; c++)
@@ -1482,7 +1107,7 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, opts, nullptr, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::opts2_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
@@ -1522,7 +1147,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, opts, nullptr, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts2_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1547,7 +1172,7 @@ int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, false, nrend);
+    return submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1555,7 +1180,7 @@ int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data,
                                int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, true, nrend);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1580,7 +1205,8 @@ int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh
     return 0;
 }
 
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size) {
+// parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2* o = &h2j::kPlainOutput, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -1588,6 +1214,8 @@ static int single_job(h2j_engine* w, const uint8_t* data, size_t size) {
     e.jobs[0].threads = e.pool->size() + 1;  // independent slices on several threads
     int r = h2j::parse_any(data, size, e.jobs[0]);
     if (r) return e.fail("parse failed: " + e.jobs[0].message);
+    h2j::resolve_outputs(o, nrend, e.jobs[0]);
+    e.jobs[0].out_base = 0;
     e.slot[0].live.assign(1, 0);
     e.slot[0].jobs = &e.jobs;
     return 0;
@@ -1595,7 +1223,7 @@ static int single_job(h2j_engine* w, const uint8_t* data, size_t size) {
 
 // copy picture k of slot s (after sync) out as uint16 cropped planes
 static int copy_planes(Engine& e, Slot& s, int k, int stage, uint16_t* planes_out, size_t cap, int* info) {
-    const h2j_frame& f = s.frames[k];
+    const h2j_frame& f = s.plan.frames[k];
     const int w_ = f.out_w, h_ = f.out_h;
     const size_t need = static_cast<size_t>(w_) * h_ * 3 / 2;
     info[0] = w_;
@@ -1645,6 +1273,7 @@ int h2j_engine_decode_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     e.par(n, [&](int i) {
         e.jobs[i].threads = 1;
         rc[i] = h2j::parse_any(data[i], sizes[i], e.jobs[i]);
+        if (rc[i] == 0) h2j::resolve_outputs(&h2j::kPlainOutput, 1, e.jobs[i]);
     });
     for (int i = 0; i < n; i++)
         if (rc[i]) {
@@ -1666,7 +1295,7 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
     if (single_job(w, data, size)) return -2;
     Slot& s = e.slot[0];
     if (e.enqueue(s, 4, false) || e.sync(s)) return -3;
-    const h2j_frame& f = s.frames[0];
+    const h2j_frame& f = s.plan.frames[0];
     const int nmcu = ((f.out_w + 15) >> 4) * ((f.out_h + 15) >> 4);
     h2j_jstat st;
     if (cap < static_cast<size_t>(nmcu) * 384) return e.fail("output buffer too small");
@@ -1693,34 +1322,21 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
             e.fail("invalid output options");
             return H2J_ERR_OUT_OPTS;
         }
-    if (single_job(w, data, size)) return -2;
-    h2j::FrameJob& job = e.jobs[0];
-    std::vector<h2j::FrameJob::Output> outs(static_cast<size_t>(nrend));
-    for (int r = 0; r < nrend; r++) {
-        h2j::resolve_output(o[r], job);
-        outs[r].scale_log2 = job.scale_log2;
-        outs[r].fit_w = job.fit_w;
-        outs[r].fit_h = job.fit_h;
-    }
-    if (nrend > 1) {
-        job.outs = outs;
-        job.scale_log2 = job.fit_w = job.fit_h = 0;
-    }
-    job.out_base = 0;
+    if (single_job(w, data, size, o, nrend)) return -2;
     Slot& s = e.slot[0];
     if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
     // the picture K4 would read: the JPEG source view of the rendition
-    const h2j_frame& f = s.frames[0];
-    const int vi = s.rends[static_cast<size_t>(pick)].view;
-    const h2j_scaled& sc = s.scaled[vi];
-    const h2j_frame v = h2j::jpeg_view(f, sc, s.vjcoef[vi]);
+    const h2j_frame& f = s.plan.frames[0];
+    const int vi = s.plan.rends[static_cast<size_t>(pick)].view;
+    const h2j_scaled& sc = s.plan.scaled[vi];
+    const h2j_frame v = s.plan.view(vi);
     const int w_ = v.out_w, h_ = v.out_h;
     int levels = 0;  // K3s levels among the views: two or more are K3p's
-    for (const h2j_scaled& x : s.scaled)
+    for (const h2j_scaled& x : s.plan.scaled)
         if (x.scale_log2 >= 1 && x.scale_log2 <= 3) levels |= 1 << x.scale_log2;
     info[0] = w_;
     info[1] = h_;
-    info[2] = (nrend > 1 && sc.scale_log2 >= 1 && sc.scale_log2 <= 3 && (levels & (levels - 1))) ? 5 : sc.scale_log2;
+    info[2] = (sc.scale_log2 >= 1 && sc.scale_log2 <= 3 && (levels & (levels - 1))) ? 5 : sc.scale_log2;
     info[3] = f.bit_depth;
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;

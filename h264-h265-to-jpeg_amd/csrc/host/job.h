@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "h2j.h"
 #include "h2j_jobs.h"
 
 namespace h2j {
@@ -26,18 +27,16 @@ struct FrameJob {
     // the second field; the reference sends one packet (one field) and returns false (only
     // H2J_STRICT_REFERENCE acts on it)
     bool field_pair = false;
-    // scaled output: the JPEG at 1/2^scale_log2 of the decoded size (the engine sets it after the
-    // parse, from the item's output options and the parsed size)
-    int scale_log2 = 0;
-    // exact-size output: scale_log2 == H2J_SCALE_RESAMPLE and the JPEG is fit_w x fit_h (h2j_fit_size of
-    // the item's options and the parsed size; a size K3s makes is given to it as scale_log2 1..3)
-    int fit_w = 0, fit_h = 0;
-    // several renditions of one picture (h2j_engine_transcode_multi): the resolved output of each, or its
-    // own error (invalid options fail that rendition alone).  Empty: one output, the fields above
+    // the item's outputs, one per rendition it asks for (a plain item: one), resolved by the engine after
+    // the parse from the rendition's options and the parsed size (resolve_output), or that rendition's own
+    // error (invalid options fail it alone).  A job that did not parse has none
     struct Output {
+        // the JPEG at 1/2^scale_log2 of the decoded size; exact-size output: H2J_SCALE_RESAMPLE and the
+        // JPEG is fit_w x fit_h (a size K3s makes is given to it as scale_log2 1..3)
         int scale_log2 = 0, fit_w = 0, fit_h = 0, error = 0;
     };
-    std::vector<Output> outs;
+    Output outs[H2J_MAX_RENDITIONS];
+    int nouts = 0;
     int out_base = 0;  // index of the item's first rendition in the batch's output arrays
 
     void clear() {
@@ -51,9 +50,7 @@ struct FrameJob {
         message.clear();
         reorder_delay = false;
         field_pair = false;
-        scale_log2 = 0;
-        fit_w = fit_h = 0;
-        outs.clear();
+        nouts = 0;
     }
 };
 

@@ -153,7 +153,7 @@ typedef struct {
        unscaled frame is its own view; a scaled frame's view is the 8-bit scaled picture K3s wrote
        at h2j_scaled.spic (crop 0, out_w x out_h = jpeg_w x jpeg_h, the spic strides and plane offsets, bit
        depth 8, pic == pic2 so that K4a sums its variances), so the K4 / K5 kernels run the same
-       code for both kinds.  The engine builds them (jpeg_view in engine.cpp); == frames, or NULL,
+       code for both kinds.  The engine builds them (ChunkPlan::view, chunk_plan.cpp); == frames, or NULL,
        when no picture of the batch is scaled.  A picture with several renditions has one view per
        distinct output (each with its own jcoef and jstat, the first the frame's own); the engine then
        runs K4 / K5 on a second descriptor whose nframes counts the views and whose frames are the views */
