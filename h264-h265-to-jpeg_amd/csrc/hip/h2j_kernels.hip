@@ -4557,10 +4557,13 @@ __global__ void __launch_bounds__(256, 8) h2j_k3_sao(const h2j_frame* __restrict
 // plane's last column / row (the edge replication of the JPEG padding, jpeg_sample).
 // A read-once stream: a workgroup is 4 output rows of 64 dwords, a lane makes 4 adjacent output
 // samples (one dword store) from S rows of 4S source samples, so a wave reads S contiguous row
-// segments of 256 S sizeof(Pel) bytes.  Rows are loaded 8 or 16 bytes at a time where the crop and
-// the row pitch keep them aligned and the 4S columns lie inside the plane (rows clamp there too:
-// a clamped row is the same load again); the other lanes -- the right edge, unaligned crops --
-// sum clamped single samples.
+// segments of 256 S sizeof(Pel) bytes.  Rows are loaded 8 or 16 bytes at a time where the row pitch
+// keeps them aligned and the 4S columns lie inside the plane (rows clamp there too: a clamped row is
+// the same load again): as they lie where the plane's first cropped sample is load-aligned, else -- a
+// window's origin (crop and cover) -- from the boundary before them and shifted into place
+// (k3s_load_row_shifted).  The other lanes -- the right edge, where a window's last column is
+// replicated although real samples lie beyond it, and planes with an unaligned pitch -- sum clamped
+// single samples.
 DEVI uint32_t k3s_pk_add_u16(uint32_t a, uint32_t b) {  // v_pk_add_u16
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b));
@@ -4582,12 +4585,98 @@ DEVI void k3s_load_row(const void* p, uint32_t (&w)[NW]) {
         }
     }
 }
+// The shifted row load (crop and cover: a window's origin is rarely load-aligned).  The row pitch is a
+// multiple of the load width LW (8 bytes at NW == 2, else 16) and the plane's first cropped sample lies m
+// bytes (0 < m < LW, a multiple of sizeof(Pel), uniform over the plane) behind an LW boundary, so every
+// lane's row segment does: `pa` is that segment's address rounded down to the boundary.  One more LW-wide
+// load than k3s_load_row, aligned loads only; dword q of the segment is bytes m + 4q .. m + 4q + 3 of what
+// was loaded: a dword offset MD = m >> 2 -- uniform; a template argument, so that registers are named and
+// never indexed (the kernels branch once per lane on it) -- and a byte funnel shift by mb = m & 3
+// (v_alignbyte_b32 with a scalar shift).
+// Every byte loaded lies inside the arena.  The first load starts at most LW - 1 bytes before the first
+// sample of a row of pic2: at worst before the plane's first row, in the plane before it or, for luma,
+// in the bytes before pic2; the last load ends at most LW - 1 bytes behind the segment: at worst behind
+// the V plane's last row, in the bytes behind pic2.  The arena's regions are 256-byte aligned and pic2 is
+// neither its first nor its last region (chunk_plan.cpp layout_arena: the zeroed maps and jstat records
+// lie before the pictures, the jcoef regions, residuals and aux behind them), so both are arena bytes.
+template <int NW, int MD>
+DEVI void k3s_load_row_shifted(const void* pa, uint32_t mb, uint32_t (&w)[NW]) {
+    constexpr int LD = NW == 2 ? 2 : 4;  // dwords per load
+    uint32_t r[NW + LD];
+    if constexpr (NW == 2) {
+        const uint2 a = reinterpret_cast<const uint2*>(pa)[0], b = reinterpret_cast<const uint2*>(pa)[1];
+        r[0] = a.x; r[1] = a.y; r[2] = b.x; r[3] = b.y;
+    } else {
+#pragma unroll
+        for (int q = 0; q < NW / 4 + 1; q++) {
+            const uint4 v = reinterpret_cast<const uint4*>(pa)[q];
+            r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
+        }
+    }
+    static_assert(MD >= 0 && MD < LD, "the dword offset lies inside one load");
+#pragma unroll
+    for (int q = 0; q < NW; q++) w[q] = __builtin_amdgcn_alignbyte(r[q + MD + 1], r[q + MD], mb);
+}
+// a lane's row segment at element offset `off` of plane P: load-aligned (MD < 0), or m = 4 MD + (m & 3) bytes
+// behind a boundary
+template <int MD, typename Pel, int NW>
+DEVI void k3s_load_row_at(const Pel* P, int off, uint32_t m, uint32_t (&w)[NW]) {
+    if constexpr (MD >= 0) k3s_load_row_shifted<NW, MD>(reinterpret_cast<const uint8_t*>(at32(P, off)) - m, m & 3u, w);
+    else k3s_load_row<NW>(at32(P, off), w);
+}
+// K3s: the sums of a lane's 4 outputs from S rows of wide loads (row0: element offset of the lane's segment
+// in plane row 0; rows clamp at the cropped plane's last row)
+template <typename Pel, int K, int MD>
+DEVI void k3s_sum_wide(const Pel* P, int row0, int y, int ph, int cy, int st, uint32_t m, unsigned (&acc)[4]) {
+    constexpr int S = 1 << K;
+    constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;
+    if constexpr (sizeof(Pel) == 1) {
+        // all S rows in flight; the shifted loads hold a load more per row, so half of 8 rows at a time
+        constexpr int G = (MD >= 0 && S == 8) ? 4 : S;
+#pragma unroll
+        for (int g = 0; g < S; g += G) {
+            uint32_t w[G][NW];
+#pragma unroll
+            for (int j = 0; j < G; j++) k3s_load_row_at<MD, Pel, NW>(P, m24(min(y * S + g + j, ph - 1) + cy, st) + row0, m, w[j]);
+#pragma unroll
+            for (int j = 0; j < G; j++)
+#pragma unroll
+                for (int o = 0; o < 4; o++) {  // S bytes per output: half a dword, one, two
+                    if constexpr (K == 1) acc[o] = __builtin_amdgcn_udot4(w[j][o >> 1], (o & 1) ? 0x01010000u : 0x00000101u, acc[o], false);
+                    else if constexpr (K == 2) acc[o] = __builtin_amdgcn_udot4(w[j][o], 0x01010101u, acc[o], false);
+                    else acc[o] = __builtin_amdgcn_udot4(w[j][2 * o], 0x01010101u,
+                                                         __builtin_amdgcn_udot4(w[j][2 * o + 1], 0x01010101u, acc[o], false), false);
+                }
+        }
+    } else {
+        // rows add up as packed 16-bit pairs, four rows at most (4 x (2^14 - 1) < 2^16: bit depths to 14)
+        constexpr int G = S < 4 ? S : 4;
+#pragma unroll
+        for (int g = 0; g < S; g += G) {
+            uint32_t w[G][NW];
+#pragma unroll
+            for (int j = 0; j < G; j++) k3s_load_row_at<MD, Pel, NW>(P, m24(min(y * S + g + j, ph - 1) + cy, st) + row0, m, w[j]);
+#pragma unroll
+            for (int q = 0; q < NW; q++) {
+                uint32_t pk = w[0][q];
+#pragma unroll
+                for (int j = 1; j < G; j++) pk = k3s_pk_add_u16(pk, w[j][q]);
+                acc[q / (S / 2)] += (pk & 0xFFFFu) + (pk >> 16);  // S / 2 dwords per output
+            }
+        }
+    }
+}
+// (K = 2: the allocator is held to the 7 waves a SIMD the kernel had before the shifted loads -- 62 VGPRs;
+// left alone it takes 77 and 6 waves, for the aligned path too)
 template <typename Pel, int K>
-__global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 2 ? 7 : 1))) h2j_k3s_downscale(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
                                                          const h2j_scaled* __restrict__ smap) {
     constexpr int S = 1 << K;
     constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;  // dwords of one source row of a lane
     constexpr int LW = NW == 2 ? 8 : 16;                            // bytes per load
+    // 16-bit samples at K = 3 keep the single samples for unaligned origins: the shifted form there holds
+    // 20 dwords a row and takes the kernel from 77 to 129 VGPRs (6 to 3 waves a SIMD), the aligned path with it
+    constexpr bool kShifted = !(sizeof(Pel) == 2 && K == 3);
     // workgroup order, timed both ways on 1024 1080p pictures (profiles/scale_k3s_order_ab.md): the
     // XCD-aware order wins at K = 1 (0.97 against 1.01 ms), the dispatcher's own order at K = 2 and 3
     // (0.58 against 0.62 and 0.61 ms) -- as grid.h records for the other read-once streams
@@ -4619,40 +4708,20 @@ __global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __rest
     const int bd = c ? f.bit_depth_c : f.bit_depth, sh = 2 * K + bd - 8;
     const Pel* P = reinterpret_cast<const Pel*>(arena + f.pic2) + f.pic_off[c];
     const int xs = xd * 4 * S;  // first source column of this lane
-    // uniform over the plane: its first cropped sample and its row pitch are load-aligned (xs is)
-    const bool aligned = (((static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) |
-                           (static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel)))) & (LW - 1)) == 0;
+    // uniform over the plane: its row pitch is load-aligned, and its first cropped sample lies m bytes behind
+    // a load boundary (xs keeps that).  m == 0: the wide loads; else, with an aligned pitch, the shifted ones
+    // (a window's origin: crop and cover); an unaligned pitch leaves the plane to the single samples
+    const uint32_t m = (static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) & (LW - 1);
+    const bool pitch_ok = ((static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel))) & (LW - 1)) == 0;
     unsigned acc[4] = {0, 0, 0, 0};
-    if (aligned && xs + 4 * S <= pw) {
-        if constexpr (sizeof(Pel) == 1) {
-            uint32_t w[S][NW];
-#pragma unroll
-            for (int j = 0; j < S; j++) k3s_load_row<NW>(at32(P, m24(min(y * S + j, ph - 1) + cy, st) + cx + xs), w[j]);
-#pragma unroll
-            for (int j = 0; j < S; j++)
-#pragma unroll
-                for (int o = 0; o < 4; o++) {  // S bytes per output: half a dword, one, two
-                    if constexpr (K == 1) acc[o] = __builtin_amdgcn_udot4(w[j][o >> 1], (o & 1) ? 0x01010000u : 0x00000101u, acc[o], false);
-                    else if constexpr (K == 2) acc[o] = __builtin_amdgcn_udot4(w[j][o], 0x01010101u, acc[o], false);
-                    else acc[o] = __builtin_amdgcn_udot4(w[j][2 * o], 0x01010101u,
-                                                         __builtin_amdgcn_udot4(w[j][2 * o + 1], 0x01010101u, acc[o], false), false);
-                }
-        } else {
-            // rows add up as packed 16-bit pairs, four rows at most (4 x (2^14 - 1) < 2^16: bit depths to 14)
-            constexpr int G = S < 4 ? S : 4;
-#pragma unroll
-            for (int g = 0; g < S; g += G) {
-                uint32_t w[G][NW];
-#pragma unroll
-                for (int j = 0; j < G; j++) k3s_load_row<NW>(at32(P, m24(min(y * S + g + j, ph - 1) + cy, st) + cx + xs), w[j]);
-#pragma unroll
-                for (int q = 0; q < NW; q++) {
-                    uint32_t pk = w[0][q];
-#pragma unroll
-                    for (int j = 1; j < G; j++) pk = k3s_pk_add_u16(pk, w[j][q]);
-                    acc[q / (S / 2)] += (pk & 0xFFFFu) + (pk >> 16);  // S / 2 dwords per output
-                }
-            }
+    if (pitch_ok && m == 0 && xs + 4 * S <= pw) {
+        k3s_sum_wide<Pel, K, -1>(P, cx + xs, y, ph, cy, st, 0u, acc);
+    } else if (kShifted && pitch_ok && xs + 4 * S <= pw) {
+        switch (m >> 2) {  // uniform
+        case 0: k3s_sum_wide<Pel, K, 0>(P, cx + xs, y, ph, cy, st, m, acc); break;
+        case 1: k3s_sum_wide<Pel, K, 1>(P, cx + xs, y, ph, cy, st, m, acc); break;
+        case 2: if constexpr (LW == 16) k3s_sum_wide<Pel, K, 2>(P, cx + xs, y, ph, cy, st, m, acc); break;
+        default: if constexpr (LW == 16) k3s_sum_wide<Pel, K, 3>(P, cx + xs, y, ph, cy, st, m, acc); break;
         }
     } else {
         for (int o = 0; o < 4; o++)
@@ -4680,7 +4749,8 @@ __global__ void __launch_bounds__(256) h2j_k3s_downscale(const h2j_frame* __rest
 // bounds-checked against its own size (a sum beyond it is of clamped samples only and is not stored).
 // A lane makes 4 adjacent outputs of level KC from 2^KC rows of 4 * 2^KC source samples -- K3s's loads
 // at K = KC -- and stores 2^(KC-k) rows of 2^(KC-k) dwords at level k.  Lanes whose columns are not all
-// inside the plane, and planes with unaligned crops or pitches, sum clamped single samples, as in K3s.
+// inside the plane, and planes with unaligned pitches, sum clamped single samples, as in K3s; unaligned origins
+// take K3s's shifted loads.
 // The dispatcher's own workgroup order, as K3s at K = 2 and 3 (the same read-once stream).
 template <int R, int C>
 DEVI void k3p_store(const unsigned (&a)[R][C], uint8_t* __restrict__ arena, const h2j_scaled& sl, int c, int xd, int y, int sh) {
@@ -4714,11 +4784,32 @@ DEVI void k3p_fold(const unsigned (&a)[2 * R][2 * C], unsigned (&b)[R][C]) {
 #pragma unroll
         for (int x = 0; x < C; x++) b[r][x] = a[2 * r][2 * x] + a[2 * r][2 * x + 1] + a[2 * r + 1][2 * x] + a[2 * r + 1][2 * x + 1];
 }
+// K3p: a lane's unrounded level-1 sums from 2^KC rows of wide loads (as k3s_sum_wide)
+template <typename Pel, int KC, int MD>
+DEVI void k3p_sum_wide(const Pel* P, int row0, int ys, int ph, int cy, int st, uint32_t m, unsigned (&a1)[(1 << KC) / 2][2 << KC]) {
+    constexpr int S = 1 << KC;
+    constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;
+#pragma unroll
+    for (int r = 0; r < S / 2; r++) {
+        uint32_t w0[NW], w1[NW];
+        k3s_load_row_at<MD, Pel, NW>(P, m24(min(ys + 2 * r, ph - 1) + cy, st) + row0, m, w0);
+        k3s_load_row_at<MD, Pel, NW>(P, m24(min(ys + 2 * r + 1, ph - 1) + cy, st) + row0, m, w1);
+#pragma unroll
+        for (int q = 0; q < NW; q++) {
+            if constexpr (sizeof(Pel) == 1) {  // a dword: two horizontal pairs
+                a1[r][2 * q] = __builtin_amdgcn_udot4(w0[q], 0x00000101u, __builtin_amdgcn_udot4(w1[q], 0x00000101u, 0u, false), false);
+                a1[r][2 * q + 1] = __builtin_amdgcn_udot4(w0[q], 0x01010000u, __builtin_amdgcn_udot4(w1[q], 0x01010000u, 0u, false), false);
+            } else {  // a dword: one horizontal pair; two rows add up packed (2 x (2^14 - 1) < 2^16)
+                const uint32_t pk = k3s_pk_add_u16(w0[q], w1[q]);
+                a1[r][q] = (pk & 0xFFFFu) + (pk >> 16);
+            }
+        }
+    }
+}
 template <typename Pel, int KC>
 __global__ void __launch_bounds__(256) h2j_k3p_pyramid(const h2j_frame* __restrict__ frames, uint8_t* __restrict__ arena,
                                                        const h2j_pyramid* __restrict__ pmap) {
     constexpr int S = 1 << KC;
-    constexpr int NW = 4 * S * static_cast<int>(sizeof(Pel)) / 4;  // dwords of one source row of a lane (16-byte loads)
     const h2j_pyramid& py = pmap[blockIdx.y];
     const h2j_frame& f = frames[py.frame];
     const h2j_scaled& sk = py.lvl[KC - 1];  // the coarsest level: the grid
@@ -4748,25 +4839,18 @@ __global__ void __launch_bounds__(256) h2j_k3p_pyramid(const h2j_frame* __restri
     const int bd = c ? f.bit_depth_c : f.bit_depth;
     const Pel* P = reinterpret_cast<const Pel*>(arena + f.pic2) + f.pic_off[c];
     const int xs = xd * 4 * S, ys = y * S;  // first source column / row of this lane
-    const bool aligned = (((static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) |
-                           (static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel)))) & 15u) == 0;
+    // as K3s (16-byte loads): m bytes behind a load boundary, the row pitch load-aligned or not
+    const uint32_t m = (static_cast<uint32_t>(f.pic2) + static_cast<uint32_t>(f.pic_off[c] + cx) * static_cast<uint32_t>(sizeof(Pel))) & 15u;
+    const bool pitch_ok = ((static_cast<uint32_t>(st) * static_cast<uint32_t>(sizeof(Pel))) & 15u) == 0;
     unsigned a1[S / 2][2 * S];  // unrounded level-1 sums: 2 x 2 source samples each
-    if (aligned && xs + 4 * S <= pw) {
-#pragma unroll
-        for (int r = 0; r < S / 2; r++) {
-            uint32_t w0[NW], w1[NW];
-            k3s_load_row<NW>(at32(P, m24(min(ys + 2 * r, ph - 1) + cy, st) + cx + xs), w0);
-            k3s_load_row<NW>(at32(P, m24(min(ys + 2 * r + 1, ph - 1) + cy, st) + cx + xs), w1);
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-                if constexpr (sizeof(Pel) == 1) {  // a dword: two horizontal pairs
-                    a1[r][2 * q] = __builtin_amdgcn_udot4(w0[q], 0x00000101u, __builtin_amdgcn_udot4(w1[q], 0x00000101u, 0u, false), false);
-                    a1[r][2 * q + 1] = __builtin_amdgcn_udot4(w0[q], 0x01010000u, __builtin_amdgcn_udot4(w1[q], 0x01010000u, 0u, false), false);
-                } else {  // a dword: one horizontal pair; two rows add up packed (2 x (2^14 - 1) < 2^16)
-                    const uint32_t pk = k3s_pk_add_u16(w0[q], w1[q]);
-                    a1[r][q] = (pk & 0xFFFFu) + (pk >> 16);
-                }
-            }
+    if (pitch_ok && m == 0 && xs + 4 * S <= pw) {
+        k3p_sum_wide<Pel, KC, -1>(P, cx + xs, ys, ph, cy, st, 0u, a1);
+    } else if (pitch_ok && xs + 4 * S <= pw) {
+        switch (m >> 2) {  // uniform
+        case 0: k3p_sum_wide<Pel, KC, 0>(P, cx + xs, ys, ph, cy, st, m, a1); break;
+        case 1: k3p_sum_wide<Pel, KC, 1>(P, cx + xs, ys, ph, cy, st, m, a1); break;
+        case 2: k3p_sum_wide<Pel, KC, 2>(P, cx + xs, ys, ph, cy, st, m, a1); break;
+        default: k3p_sum_wide<Pel, KC, 3>(P, cx + xs, ys, ph, cy, st, m, a1); break;
         }
     } else {
 #pragma unroll

@@ -30,8 +30,8 @@ bool k3s_level(const h2j_scaled& sc) { return sc.scale_log2 >= 1 && sc.scale_log
 size_t view_blocks(const h2j_scaled& sc) { return static_cast<size_t>(((sc.jpeg_w + 15) >> 4) * ((sc.jpeg_h + 15) >> 4)) * 6; }
 bool banded(const h2j_frame& f) { return f.codec == H2J_CODEC_H264 && f.k1bands > 1; }
 
-// Number the frames' records, and give every frame its views: one per distinct output of its
-// renditions, the unscaled one first.  A view's JPEG size is the cropped picture's, its scaled size or
+// Number the frames' records, and give every frame its views: one per distinct (window, output) of its
+// renditions, the unscaled whole picture first.  A view's JPEG size is the cropped picture's, its scaled size or
 // its fit size (K4 / K5 work on that picture)
 void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p) {
     size_t ntu = 0, ncoef = 0, nctb = 0, nslice = 0, nsl = 0;
@@ -58,25 +58,36 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
         // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
         f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
         f.xline = 0;
-        const size_t v0 = p.scaled.size();
+        const size_t v0 = p.scaled.size(), w0 = p.wins.size();
         p.vfirst[k] = static_cast<int>(v0);
-        auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this output, added if new
+        auto source_of = [&](const FrameJob::Output& o) {  // the frame, or nf + the frame's window, added if new
+            if (!o.windowed) return k;
+            for (size_t w = w0; w < p.wins.size(); w++)
+                if (p.wins[w].x == o.win_x && p.wins[w].y == o.win_y && p.wins[w].w == o.win_w && p.wins[w].h == o.win_h)
+                    return p.nf + static_cast<int>(w);
+            p.wins.push_back(ChunkPlan::Window{k, o.win_x, o.win_y, o.win_w, o.win_h});
+            return p.nf + static_cast<int>(p.wins.size()) - 1;
+        };
+        auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this window and output, added if new
+            const int src = source_of(o);
             for (size_t v = v0; v < p.scaled.size(); v++) {
                 const h2j_scaled& sv = p.scaled[v];
-                if (sv.scale_log2 == o.scale_log2 && (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
+                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 &&
+                    (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
                     return static_cast<int>(v);
             }
             h2j_scaled sc{};
             sc.frame = k;
             sc.scale_log2 = o.scale_log2;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
-            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(f.out_w, sc.scale_log2);
-            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(f.out_h, sc.scale_log2);
+            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(o.windowed ? o.win_w : f.out_w, sc.scale_log2);
+            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(o.windowed ? o.win_h : f.out_h, sc.scale_log2);
             p.scaled.push_back(sc);
+            p.vsrc.push_back(src);
             return static_cast<int>(p.scaled.size()) - 1;
         };
         for (int r = 0; r < j.nouts; r++)
-            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0) {
+            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed) {
                 view_of(j.outs[r]);
                 break;
             }
@@ -98,7 +109,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     p.seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(p.nv);
     // the records' places in the staging buffer
     Cursor c;
-    p.at.frames = c.take(p.nf * sizeof(h2j_frame));
+    p.at.frames = c.take((p.nf + p.wins.size()) * sizeof(h2j_frame));
     p.at.tus = c.take(ntu * sizeof(h2j_tu));
     p.at.coefs = c.take(ncoef * sizeof(h2j_coef));
     p.at.ctbs = c.take(nctb * sizeof(h2j_ctb));
@@ -120,6 +131,14 @@ void layout_arena(ChunkPlan& p) {
         h2j_scaled& sc = p.scaled[v];
         sc.jstat = a.take(p.jstat_stride);
         if (v == p.vfirst[sc.frame]) p.frames[sc.frame].jstat = sc.jstat;
+    }
+    p.njstat = p.nv;
+    for (int k = 0; k < p.nf; k++) {  // ... unless that view is an unscaled window (ChunkPlan::fstat)
+        const int v = p.vfirst[k];
+        p.fstat[k] = v;
+        if (p.vsrc[v] == k || p.scaled[v].scale_log2 != 0) continue;
+        p.fstat[k] = p.njstat++;
+        p.frames[k].jstat = a.take(p.jstat_stride);
     }
     p.zero_bytes = a.off;
     for (int pass = 0; pass < 2; pass++)
@@ -256,25 +275,31 @@ void build_sao_classes(ChunkPlan& p) {
 // entry per level, by class (sample type, coarsest level)
 void build_scale_classes(ChunkPlan& p) {
     h2j_gpu_batch& d = p.desc;
-    std::vector<int> levels(static_cast<size_t>(p.nf), 0);  // per frame: mask of its K3s levels
+    // per source (a frame, or nf + a window: the index the kernels find it under): mask of its K3s levels
+    const int ns = p.nf + static_cast<int>(p.wins.size());
+    std::vector<int> levels(static_cast<size_t>(ns), 0);
     int npyr = 0;
     for (int v = 0; v < p.nv && p.nv > p.nf; v++)
-        if (k3s_level(p.scaled[v])) levels[p.scaled[v].frame] |= 1 << p.scaled[v].scale_log2;
-    for (int k = 0; k < p.nf; k++) {
+        if (k3s_level(p.scaled[v])) levels[p.vsrc[v]] |= 1 << p.scaled[v].scale_log2;
+    for (int k = 0; k < ns; k++) {
         if (levels[k] & (levels[k] - 1)) npyr++;
         else levels[k] = 0;  // one level: K3s
     }
     for (int cls = 0; cls < H2J_PYR_CLASSES && npyr; cls++) {
         d.pyr_first[cls] = static_cast<int>(p.pyrmap.size());
-        for (int k = 0; k < p.nf; k++) {
+        for (int k = 0; k < ns; k++) {
             if (!levels[k]) continue;
+            const int fr = k < p.nf ? k : p.wins[k - p.nf].frame;
             const int kc = (levels[k] & 8) ? 3 : 2;
-            if (2 * (p.frames[k].bit_depth > 8 ? 1 : 0) + kc - 2 != cls) continue;
+            if (2 * (p.frames[fr].bit_depth > 8 ? 1 : 0) + kc - 2 != cls) continue;
             h2j_pyramid py{};
             py.frame = k;
             py.mask = levels[k];
-            for (int v = p.vfirst[k]; v < p.vfirst[k + 1]; v++)
-                if (k3s_level(p.scaled[v])) py.lvl[p.scaled[v].scale_log2 - 1] = p.scaled[v];
+            for (int v = p.vfirst[fr]; v < p.vfirst[fr + 1]; v++)
+                if (k3s_level(p.scaled[v]) && p.vsrc[v] == k) {
+                    py.lvl[p.scaled[v].scale_log2 - 1] = p.scaled[v];
+                    py.lvl[p.scaled[v].scale_log2 - 1].frame = k;
+                }
             p.pyrmap.push_back(py);
             d.pyr_count[cls]++;
             d.pyr_tiles[cls] = std::max(d.pyr_tiles[cls], h2j_k3s_tiles(py.lvl[kc - 1].jpeg_w, py.lvl[kc - 1].jpeg_h));
@@ -282,12 +307,14 @@ void build_scale_classes(ChunkPlan& p) {
     }
     for (int cls = 0; cls < H2J_SCALE_CLASSES && p.views; cls++) {
         d.scale_first[cls] = static_cast<int>(p.scalemap.size());
-        for (const h2j_scaled& sc : p.scaled) {
-            if (sc.scale_log2 == 0 || (levels[sc.frame] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
+        for (int v = 0; v < p.nv; v++) {
+            const h2j_scaled& sc = p.scaled[v];
+            if (sc.scale_log2 == 0 || (levels[p.vsrc[v]] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
             const int hbd = p.frames[sc.frame].bit_depth > 8 ? 1 : 0;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
             if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
             p.scalemap.push_back(sc);
+            p.scalemap.back().frame = p.vsrc[v];  // the kernel's source: the frame, or the window's copy of it
             d.scale_count[cls]++;
             d.scale_tiles[cls] = std::max(d.scale_tiles[cls], resample ? h2j_k3r_tiles(sc.jpeg_w, sc.jpeg_h) : h2j_k3s_tiles(sc.jpeg_w, sc.jpeg_h));
         }
@@ -334,8 +361,9 @@ void fill_descriptor(ChunkPlan& p) {
     d.k1hevc_n = static_cast<int32_t>(p.k1hevc.size());
     // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
     // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
-    for (const h2j_scaled& sc : p.scaled)
-        d.k4a_frames += (h2j_sao_folds_variance(p.frames[sc.frame]) && sc.scale_log2 == 0) ? 0 : 1;
+    // (a window: always K4a, on the window)
+    for (int v = 0; v < p.nv; v++)
+        d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf) ? 0 : 1;
 }
 
 }  // namespace
@@ -348,6 +376,14 @@ h2j_frame ChunkPlan::view(int v) const {
     h2j_frame f = frames[sc.frame];
     f.jcoef = vjcoef[v];
     f.jstat = sc.jstat;
+    if (sc.scale_log2 == 0 && vsrc[v] >= nf) {  // an unscaled window: the frame in place, its crop moved
+        const h2j_frame w = wframe(vsrc[v] - nf);
+        f.crop_x = w.crop_x;
+        f.crop_y = w.crop_y;
+        f.out_w = w.out_w;
+        f.out_h = w.out_h;
+        f.pic = f.pic2;  // pic == pic2: K4a sums the window's MB variances (K3 SAO summed the whole picture's)
+    }
     if (sc.scale_log2 == 0) return f;
     f.pic = f.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
     f.crop_x = f.crop_y = 0;
@@ -361,12 +397,25 @@ h2j_frame ChunkPlan::view(int v) const {
     return f;
 }
 
+h2j_frame ChunkPlan::wframe(int j) const {
+    const Window& w = wins[j];
+    h2j_frame f = frames[w.frame];
+    f.crop_x += w.x;
+    f.crop_y += w.y;
+    f.out_w = w.w;
+    f.out_h = w.h;
+    return f;
+}
+
 void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p) {
     p.nf = static_cast<int>(live.size());
     p.frames.resize(static_cast<size_t>(p.nf));
     p.vfirst.assign(static_cast<size_t>(p.nf) + 1, 0);
     for (auto* m : {&p.k1map, &p.k1map8, &p.k1all, &p.k1hevc, &p.saomap}) m->clear();
     p.scaled.clear();
+    p.vsrc.clear();
+    p.wins.clear();
+    p.fstat.assign(static_cast<size_t>(p.nf), 0);
     p.rends.clear();
     p.scalemap.clear();
     p.pyrmap.clear();
@@ -374,7 +423,7 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     std::memset(&p.desc, 0, sizeof(p.desc));
     number_frames_and_views(jobs, live, p);
     // scaled pictures present, or several renditions of a frame: a views array is uploaded
-    p.views = p.nv > p.nf || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; });
+    p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; });
     p.vjcoef.resize(static_cast<size_t>(p.nv));
     layout_arena(p);
     build_k1_maps(p);

@@ -21,7 +21,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct ChunkPlan {
     // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
-    // is (frame, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
+    // is (frame, window, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
     // the first view of a frame -- its unscaled rendition if it has one -- keeps the frame's own jcoef
     // and jstat.  One rendition per item: nv == nf, view k is frame k
     int nf = 0, nv = 0;
@@ -33,6 +33,24 @@ struct ChunkPlan {
         int out, view;  // index in the batch's output arrays; the view that holds its JPEG
     };
     std::vector<Rend> rends;  // the chunk's renditions (those with valid options), frame-major
+
+    // Windows (crop and cover): a distinct (frame, window) pair is uploaded as a copy of the frame behind the
+    // nf frames, with the window added to its conformance crop (wframe), so that K3s, K3r and K3p read "the
+    // cropped planes of pic2" of the copy with the code they have; K0 .. K3 walk the nf frames only.  An
+    // unscaled windowed view needs no kernel: K4 reads the frame in place through the view (view()).
+    // A chunk without windows has none of this and uploads what it always did
+    struct Window {
+        int frame, x, y, w, h;  // the frame, and the window in luma samples of its cropped picture
+    };
+    std::vector<Window> wins;  // the chunk's distinct windows, frame-major
+    std::vector<int> vsrc;     // per view: the index the scale kernels find its source under -- its frame, or
+                               // nf + its window; views of one source with K3s levels form one pyramid
+    std::vector<int> fstat;    // per frame: the jstat slot (of njstat) that is the frame's own -- its first
+                               // view's, or one behind the views' when that view is an unscaled window (the
+                               // frame's jstat takes K3 SAO's variance sum of the whole picture and the
+                               // device-side error flags; the window's sum is K4a's, in the view's own)
+    int njstat = 0;            // jstat slots: nv, and one more per such frame
+    h2j_frame wframe(int j) const;  // the frame copy of window j
 
     // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
@@ -60,7 +78,7 @@ struct ChunkPlan {
     h2j_frame view(int v) const;
 };
 
-// Plan the chunk of jobs[live[0..]] (parsed jobs, each with at least one output) into p; p's vectors are
+// Plan the chunk of jobs[live[0..]] (parsed jobs, each with at least one valid output: every frame has a view) into p; p's vectors are
 // reused from chunk to chunk.
 void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p);
 

@@ -54,8 +54,8 @@ struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
     // the options of the picture's renditions: one (all 0: the decoded size; h2j_h265_to_jpeg_mem_scaled,
-    // _fit) or several (h2j_h265_to_jpeg_mem_multi); per rendition the JPEG and status once the batch ran
-    std::vector<h2j_out_opts2> opts{h2j_out_opts2{0, 0, 0, 0, 0, {0, 0, 0}}};
+    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3); per rendition the JPEG and status once the batch ran
+    std::vector<h2j_out_opts3> opts{h2j_out_opts3{0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}}};
     std::vector<std::vector<uint8_t>> jpegs;
     std::vector<int> rstatus;
     int status = 0;  // of the first rendition, which is all a plain caller asks for (-1: the batch did not run)
@@ -114,7 +114,7 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
 }
 
 // run one batch (caller holds no lock); fills jpegs / rstatus / status / error of each request.  Every
-// picture is decoded once (h2j_engine_transcode_multi; a plain request is an item with one rendition)
+// picture is decoded once (h2j_engine_transcode_multi3; a plain request is an item with one rendition)
 void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
     if (n == 0) return;
@@ -122,7 +122,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<size_t> sizes(n);
     std::vector<int32_t> nrend(n);
     std::vector<int> base(n + 1, 0);
-    std::vector<h2j_out_opts2> opts;
+    std::vector<h2j_out_opts3> opts;
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
         const Request* q = batch[i];
@@ -140,7 +140,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = h2j_engine_transcode_multi(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
+        r = h2j_engine_transcode_multi3(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
                                        len.data(), status.data());
         bool small = false;
         for (int i = 0; i < total; i++) small = small || status[i] == -50;
@@ -280,6 +280,10 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
 }
 
+static h2j_out_opts3 opts3_of(const h2j_out_opts2& o) {
+    return h2j_out_opts3{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
+}
+
 static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& opts, uint8_t** jpeg, size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
     *jpeg = nullptr;
@@ -288,7 +292,7 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts[0] = opts;
+    req.opts[0] = opts3_of(opts);
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -314,6 +318,15 @@ extern "C" int h2j_h265_to_jpeg_mem_fit(const uint8_t* data, size_t size, int fi
 
 extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, uint8_t** jpeg,
                                           size_t* jpeg_len, int* status) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (!opts) return -1;
+    std::vector<h2j_out_opts3> o3;
+    for (int r = 0; r < nrend; r++) o3.push_back(opts3_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi3(data, size, nrend, o3.data(), jpeg, jpeg_len, status);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_multi3(const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!jpeg || !jpeg_len || !status || !opts) return -1;
     for (int r = 0; r < nrend; r++) {

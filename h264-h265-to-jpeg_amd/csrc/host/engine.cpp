@@ -176,14 +176,23 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
-// Output options: h2j_out_opts2 is the engine's one option type (an h2j_out_opts item has the fit fields 0)
-const h2j_out_opts2 kPlainOutput = {0, 0, 0, 0, 0, {0, 0, 0}};  // the JPEG at the decoded size
-std::vector<h2j_out_opts2> opts2_of(int n, const h2j_out_opts* o) {  // o null: all plain
-    std::vector<h2j_out_opts2> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+// Output options: h2j_out_opts3 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
+// an h2j_out_opts2 item the crop fields)
+const h2j_out_opts3 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};  // the JPEG at the decoded size
+std::vector<h2j_out_opts3> opts3_of(int n, const h2j_out_opts* o) {  // o null: all plain
+    std::vector<h2j_out_opts3> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
     for (int i = 0; o && i < n; i++) {
         v[i].scale_log2 = o[i].scale_log2;
         v[i].max_dim = o[i].max_dim;
     }
+    return v;
+}
+h2j_out_opts3 opts3_of(const h2j_out_opts2& o) {
+    return h2j_out_opts3{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
+}
+std::vector<h2j_out_opts3> opts3_of(int n, const h2j_out_opts2* o) {
+    std::vector<h2j_out_opts3> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+    for (int i = 0; o && i < n; i++) v[i] = opts3_of(o[i]);
     return v;
 }
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
@@ -193,28 +202,60 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
     return (fit_w == 0 || (fit_w >= 2 && fit_w <= 65535)) && (fit_h == 0 || (fit_h >= 2 && fit_h <= 65535)) &&
            (flags & ~H2J_FIT_STRETCH) == 0 && !((flags & H2J_FIT_STRETCH) && fit_w == 0 && fit_h == 0);
 }
-bool out_opts_valid(const h2j_out_opts2& o) {
+// what can be said of the options before the picture's size is known (an item none of whose renditions
+// passes is not parsed); the window's place in the picture is checked by resolve_output
+bool out_opts_valid(const h2j_out_opts3& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (o.reserved[0] || o.reserved[1] || o.reserved[2] || !fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
+    if (o.reserved[0] || o.reserved[1] || o.reserved[2]) return false;
+    if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
+    if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
+        if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
+        return fit_valid(o.fit_w, o.fit_h, 0);
+    }
+    if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts2& o, int w, int h) {
+int resolve_scale(const h2j_out_opts3& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
     return k;
 }
-// the output of a w x h picture (its parsed, cropped size) with valid options.  A fit that resolves to the
-// picture's own size is the unscaled output; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k:
-// the resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest
-FrameJob::Output resolve_output(const h2j_out_opts2& o, int w, int h) {
+// the output of a W x H picture (its parsed, cropped size) with options that passed out_opts_valid: the
+// window (include/h2j.h "Crop and cover"; error H2J_ERR_OUT_OPTS if it does not lie in the picture), then
+// what the remaining options make of a picture of the window's size.  A fit that resolves to the window's own
+// size is the unscaled output; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k: the
+// resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest
+FrameJob::Output resolve_output(const h2j_out_opts3& o, int W, int H) {
     FrameJob::Output out;
-    out.scale_log2 = resolve_scale(o, w, h);
-    int ow = w, oh = h;
-    if ((o.fit_w == 0 && o.fit_h == 0) || h2j_fit_size(w, h, o.fit_w, o.fit_h, o.flags, &ow, &oh) != 0) return out;
-    if (ow == w && oh == h) return out;
+    int64_t x = o.crop_x, y = o.crop_y, w = o.crop_w ? o.crop_w : W - x, h = o.crop_h ? o.crop_h : H - y;
+    if (w < 2 || h < 2 || x + w > W || y + h > H) {
+        out.error = H2J_ERR_OUT_OPTS;
+        return out;
+    }
+    int fit_w = o.fit_w, fit_h = o.fit_h, flags = o.flags;
+    if (flags & H2J_FIT_COVER) {  // the largest centred part of the window with the box's aspect, then a stretch
+        const int64_t bw = fit_w, bh = fit_h;
+        int64_t cw = w, ch = h;
+        if (w * bh >= h * bw) cw = std::min(std::max<int64_t>(2 * ((h * bw) / (2 * bh)), 2), w);
+        else ch = std::min(std::max<int64_t>(2 * ((w * bh) / (2 * bw)), 2), h);
+        x += 2 * ((w - cw) / 4);
+        y += 2 * ((h - ch) / 4);
+        w = cw;
+        h = ch;
+        flags = H2J_FIT_STRETCH;
+    }
+    out.win_x = static_cast<int>(x);
+    out.win_y = static_cast<int>(y);
+    out.win_w = static_cast<int>(w);
+    out.win_h = static_cast<int>(h);
+    out.windowed = !(x == 0 && y == 0 && w == W && h == H);
+    out.scale_log2 = resolve_scale(o, out.win_w, out.win_h);
+    int ow = out.win_w, oh = out.win_h;
+    if ((fit_w == 0 && fit_h == 0) || h2j_fit_size(out.win_w, out.win_h, fit_w, fit_h, flags, &ow, &oh) != 0) return out;
+    if (ow == out.win_w && oh == out.win_h) return out;
     for (int k = 1; k <= 3; k++)
-        if ((ow << k) == w && (oh << k) == h) {
+        if ((ow << k) == out.win_w && (oh << k) == out.win_h) {
             out.scale_log2 = k;
             return out;
         }
@@ -223,15 +264,22 @@ FrameJob::Output resolve_output(const h2j_out_opts2& o, int w, int h) {
     out.fit_h = oh;
     return out;
 }
-std::string out_opts_message(const h2j_out_opts2& o) {
-    return "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
+// W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
+// message they always got
+std::string out_opts_message(const h2j_out_opts3& o, int W = 0, int H = 0) {
+    std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
            " (stretch needs a size), reserved " + ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
+    if (!(o.crop_x || o.crop_y || o.crop_w || o.crop_h || (o.flags & H2J_FIT_COVER))) return m;
+    m += "; crop " + std::to_string(o.crop_x) + ", " + std::to_string(o.crop_y) + ", " + std::to_string(o.crop_w) + " x " +
+         std::to_string(o.crop_h) + " (even, >= 0, at least 2 x 2 inside the picture; cover needs a box and excludes stretch, scale_log2, max_dim)";
+    if (W > 0 && H > 0) m += "; the picture is " + std::to_string(W) + " x " + std::to_string(H);
+    return m;
 }
 // the outputs of a parsed job: every rendition's is resolved on its own, and invalid options fail that
 // rendition alone
-void resolve_outputs(const h2j_out_opts2* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts3* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
@@ -241,7 +289,7 @@ void resolve_outputs(const h2j_out_opts2* o, int nr, FrameJob& job) {
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts2* o, int nr, FrameJob& job, bool* ran) {
+int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts3* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -338,7 +386,7 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts2> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    std::vector<h2j_out_opts3> opts;           // output options per rendition, item-major (a plain item has one rendition)
     std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
     int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
@@ -462,7 +510,7 @@ int Engine::ensure_buffers(Slot& s) {
     if (!s.entropy) return 0;
     if (!s.d_seg.ensure(p.seg_cap)) return fail(dev_failed + h2j_gpu_last_error());
     if (!s.d_scratch.ensure(static_cast<size_t>(p.nv) * p.tiles * 4 + 256)) return fail(dev_failed + h2j_gpu_last_error());
-    if (!s.h_js.ensure(static_cast<size_t>(p.nv) * p.jstat_stride + 256)) return fail("pinned host allocation failed");
+    if (!s.h_js.ensure(static_cast<size_t>(p.njstat) * p.jstat_stride + 256)) return fail("pinned host allocation failed");
     return 0;
 }
 
@@ -474,6 +522,10 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
         if (bytes) std::memcpy(hin + at, src, bytes);
     };
     put(p.at.frames, p.frames.data(), p.nf * sizeof(h2j_frame));
+    for (size_t j = 0; j < p.wins.size(); j++) {  // the windows' frame copies, behind the nf frames
+        const h2j_frame wf = p.wframe(static_cast<int>(j));
+        put(p.at.frames + (p.nf + j) * sizeof(h2j_frame), &wf, sizeof(wf));
+    }
     put(p.at.k1map, p.k1map.data(), p.k1map.size() * 4);
     put(p.at.k1all, p.k1all.data(), p.k1all.size() * 4);
     put(p.at.sao, p.saomap.data(), p.saomap.size() * 4);
@@ -575,7 +627,7 @@ int Engine::launch(Slot& s, const Slot* after) {
     if (s.entropy) {
         r |= h2j_gpu_memcpy_d2h(s.h_js.p, s.d_scratch.p, 8, st);  // seg_total
         r |= h2j_gpu_memcpy_d2h(s.h_js.p + 256, static_cast<uint8_t*>(s.d_arena.p) + p.jstat_base,
-                                static_cast<size_t>(p.nv) * p.jstat_stride, st);
+                                static_cast<size_t>(p.njstat) * p.jstat_stride, st);
         if (r) return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
     }
     h2j_gpu_event_record(s.ev[EV_STATS], st);
@@ -740,7 +792,8 @@ static double hbm_estimate(const FrameJob& j) {
     // (a scaled picture's 8-bit planes add 1.5 / 4^k B per sample, a resized picture's 1.5 W_o H_o B; its
     // JPEG regions shrink by more)
     const FrameJob::Output o0 = j.nouts ? j.outs[0] : FrameJob::Output();  // the first output (none: a failed job)
-    const double spic = o0.scale_log2 == H2J_SCALE_RESAMPLE ? 1.5 * o0.fit_w * o0.fit_h : o0.scale_log2 ? 1.5 * px / (1 << 2 * o0.scale_log2) : 0.0;
+    const double opx0 = o0.windowed ? static_cast<double>(o0.win_w) * o0.win_h : px;  // the output's source: a window, or the picture
+    const double spic = o0.scale_log2 == H2J_SCALE_RESAMPLE ? 1.5 * o0.fit_w * o0.fit_h : o0.scale_log2 ? 1.5 * opx0 / (1 << 2 * o0.scale_log2) : 0.0;
     double est = px * (j.hdr.bit_depth > 8 ? 24.0 : 20.0) + spic + (1 << 20);
     // several renditions: each output beyond the first adds its 8-bit planes (1.5 B per output sample), its
     // jcoef / tile region and its share of the payload pool (272 B per 8x8 block each: 6.4 B per sample),
@@ -749,7 +802,7 @@ static double hbm_estimate(const FrameJob& j) {
         const FrameJob::Output& o = j.outs[r];
         if (o.error) continue;
         const double opx = o.scale_log2 == H2J_SCALE_RESAMPLE ? static_cast<double>(o.fit_w) * o.fit_h
-                                                               : static_cast<double>(j.hdr.out_w) * j.hdr.out_h / (1 << 2 * o.scale_log2);
+                                                               : static_cast<double>(o.win_w) * o.win_h / (1 << 2 * o.scale_log2);
         est += 14.5 * opx + 8192;
     }
     return est;
@@ -841,7 +894,7 @@ void Engine::drive_loop() {
                 for (int o = b->rbase[i]; o < b->rbase[i + 1]; o++) {
                     if (b->status[o] == 0) continue;
                     if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
-                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)]);
+                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h);
                 }
             }
         if (b->jobset >= 0) jobset_busy[b->jobset] = false;
@@ -882,7 +935,7 @@ int Engine::run_batch(Batch& b) {
         for (int q = 0; q < nr; q++) {
             const int i = p.rends[q].out, k = p.rends[q].view;
             // a device-side failure (e.g. a K1 band hand-off timed out) is recorded in the frame's own jstat
-            const h2j_jstat* stf = reinterpret_cast<const h2j_jstat*>(js + p.vfirst[p.scaled[k].frame] * p.jstat_stride);
+            const h2j_jstat* stf = reinterpret_cast<const h2j_jstat*>(js + p.fstat[p.scaled[k].frame] * p.jstat_stride);
             at[q] = ~static_cast<size_t>(0);
             if (stf->dev_error) {
                 status[i] = -52;
@@ -973,7 +1026,11 @@ int Engine::run_batch(Batch& b) {
                 // a failed item fails every rendition; else each rendition's own options decide
                 for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++)
                     status[o] = jobs[k].error ? jobs[k].error : jobs[k].outs[o - b.rbase[k]].error;
-                if (jobs[k].error == 0) s.live.push_back(k);
+                // a parsed item none of whose renditions is valid (every window outside the picture) has no
+                // view: it gets no frame in the chunk, its renditions have their statuses
+                bool any_output = false;
+                for (int r = 0; r < jobs[k].nouts; r++) any_output = any_output || jobs[k].outs[r].error == 0;
+                if (jobs[k].error == 0 && any_output) s.live.push_back(k);
             }
             Slot& prev = slot[(sc + 1) & 1];
             if (enqueue(s, 4, true, true, &prev)) { fail = 1; break; }
@@ -1055,7 +1112,7 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            const h2j_out_opts3* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                             int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
@@ -1107,14 +1164,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::opts2_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::opts3_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts3_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1147,7 +1204,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts2_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts3_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1155,21 +1212,35 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts3_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
 // nrend[i] in 1..H2J_MAX_RENDITIONS for every item, and options for them
-static bool renditions_valid(int n, const int32_t* nrend, const h2j_out_opts2* opts) {
+static bool renditions_valid(int n, const int32_t* nrend, const void* opts) {
     if (n < 0 || (n > 0 && (!nrend || !opts))) return false;
     for (int i = 0; i < n; i++)
         if (nrend[i] < 1 || nrend[i] > H2J_MAX_RENDITIONS) return false;
     return true;
 }
+// the h2j_out_opts3 items of a multi call's h2j_out_opts2 items (valid counts)
+static std::vector<h2j_out_opts3> multi_opts3(int n, const int32_t* nrend, const h2j_out_opts2* opts) {
+    int total = 0;
+    for (int i = 0; i < n; i++) total += nrend[i];
+    return h2j::opts3_of(total, opts);
+}
 
 int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                 int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    return submit_batch(w, n, data, sizes, nrend, multi_opts3(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+}
+
+int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                 const h2j_out_opts3* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
     return submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, false);
@@ -1180,8 +1251,32 @@ int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data,
                                int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, multi_opts3(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+int h2j_engine_transcode_multi3(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts3* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
     const int64_t t = submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
+}
+
+int h2j_crop_window(int w, int h, const h2j_out_opts3* o, int32_t* win, int* ow, int* oh) {
+    if (!o || !win || !ow || !oh || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || !h2j::out_opts_valid(*o))
+        return H2J_ERR_OUT_OPTS;
+    const h2j::FrameJob::Output out = h2j::resolve_output(*o, w, h);
+    if (out.error) return out.error;
+    win[0] = out.win_x;
+    win[1] = out.win_y;
+    win[2] = out.win_w;
+    win[3] = out.win_h;
+    const bool resample = out.scale_log2 == H2J_SCALE_RESAMPLE;
+    *ow = resample ? out.fit_w : h2j_scaled_dim(out.win_w, out.scale_log2);
+    *oh = resample ? out.fit_h : h2j_scaled_dim(out.win_h, out.scale_log2);
+    return 0;
 }
 
 int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh) {
@@ -1206,7 +1301,7 @@ int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2* o = &h2j::kPlainOutput, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts3* o = &h2j::kPlainOutput, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -1313,8 +1408,8 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts2* o, int nrend, int pick,
-                              uint8_t* planes_out, size_t cap, int* info) {
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts3* o, int nrend, int pick,
+                              uint8_t* planes_out, size_t cap, int* info, bool window_info = false) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
     for (int r = 0; r < nrend; r++)
@@ -1323,6 +1418,11 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
             return H2J_ERR_OUT_OPTS;
         }
     if (single_job(w, data, size, o, nrend)) return -2;
+    for (int r = 0; r < nrend; r++)
+        if (e.jobs[0].outs[r].error) {  // a window outside the picture
+            e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h));
+            return H2J_ERR_OUT_OPTS;
+        }
     Slot& s = e.slot[0];
     if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
     // the picture K4 would read: the JPEG source view of the rendition
@@ -1331,13 +1431,21 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
     const h2j_scaled& sc = s.plan.scaled[vi];
     const h2j_frame v = s.plan.view(vi);
     const int w_ = v.out_w, h_ = v.out_h;
-    int levels = 0;  // K3s levels among the views: two or more are K3p's
-    for (const h2j_scaled& x : s.plan.scaled)
-        if (x.scale_log2 >= 1 && x.scale_log2 <= 3) levels |= 1 << x.scale_log2;
+    int levels = 0;  // K3s levels among the views of the same window: two or more are K3p's
+    for (int x = 0; x < s.plan.nv; x++)
+        if (s.plan.scaled[x].scale_log2 >= 1 && s.plan.scaled[x].scale_log2 <= 3 && s.plan.vsrc[x] == s.plan.vsrc[vi])
+            levels |= 1 << s.plan.scaled[x].scale_log2;
     info[0] = w_;
     info[1] = h_;
     info[2] = (sc.scale_log2 >= 1 && sc.scale_log2 <= 3 && (levels & (levels - 1))) ? 5 : sc.scale_log2;
     info[3] = f.bit_depth;
+    if (window_info) {
+        const h2j::FrameJob::Output& wo = e.jobs[0].outs[pick];
+        info[4] = wo.win_x;
+        info[5] = wo.win_y;
+        info[6] = wo.win_w;
+        info[7] = wo.win_h;
+    }
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
     size_t bytes = 0;  // the view's planes in the arena, from v.pic2
@@ -1366,21 +1474,28 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts2 o = {scale_log2, max_dim, 0, 0, 0, {0, 0, 0}};
+    const h2j_out_opts3 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts2 o = {0, 0, fit_w, fit_h, flags, {0, 0, 0}};
+    const h2j_out_opts3 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, {0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_multi(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, int pick,
                             uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (pick < 0 || pick >= nrend || !opts) return -1;
+    return decode_jpeg_source(w, data, size, h2j::opts3_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
+}
+
+int h2j_engine_decode_multi3(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, int pick,
+                             uint8_t* planes_out, size_t cap, int* info) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend) return -1;
-    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info);
+    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, true);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

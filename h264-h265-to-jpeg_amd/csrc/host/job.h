@@ -34,6 +34,11 @@ struct FrameJob {
         // the JPEG at 1/2^scale_log2 of the decoded size; exact-size output: H2J_SCALE_RESAMPLE and the
         // JPEG is fit_w x fit_h (a size K3s makes is given to it as scale_log2 1..3)
         int scale_log2 = 0, fit_w = 0, fit_h = 0, error = 0;
+        // the window of the cropped picture the output shows (crop and cover), in luma samples; the scale
+        // and the fit act on it.  windowed is false for the whole picture, whatever named it: such an
+        // output is the one without a window
+        int win_x = 0, win_y = 0, win_w = 0, win_h = 0;
+        bool windowed = false;
     };
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;

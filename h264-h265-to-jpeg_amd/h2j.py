@@ -30,7 +30,16 @@ class OutOpts2(ctypes.Structure):
                 ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
+class OutOpts3(ctypes.Structure):
+    """include/h2j.h h2j_out_opts3: h2j_out_opts2 and a window of the picture (crop and cover)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
+FIT_COVER = 2  # include/h2j.h H2J_FIT_COVER
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
 MAX_RENDITIONS = 8  # include/h2j.h H2J_MAX_RENDITIONS: JPEG outputs of one item of a multi call
 ERR_RENDITIONS = -61  # include/h2j.h H2J_ERR_RENDITIONS: a rendition count outside 1..MAX_RENDITIONS
@@ -121,6 +130,24 @@ def load_library() -> ctypes.CDLL:
         lib.h2j_h265_to_jpeg_mem_multi.restype = ctypes.c_int
         lib.h2j_h265_to_jpeg_mem_multi.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt2p, ctypes.POINTER(u8p), szp,
                                                    ctypes.POINTER(ctypes.c_int)]
+    # crop and cover (a window of the picture): likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_multi3"):
+        opt3p = ctypes.POINTER(OutOpts3)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi3.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi3.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt3p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_multi3.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi3.argtypes = lib.h2j_engine_transcode_multi3.argtypes
+        lib.h2j_engine_decode_multi3.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi3.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt3p, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi3.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi3.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt3p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_crop_window.restype = ctypes.c_int
+        lib.h2j_crop_window.argtypes = [ctypes.c_int, ctypes.c_int, opt3p, i32p, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -208,14 +235,23 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover")
+
+
+def _is_window(v):
+    """An (x, y, w, h) window of ints (w, h 0 or None: to the right / bottom edge)."""
+    return (isinstance(v, (tuple, list)) and len(v) == 4 and
+            all(x is None or (isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))) for x in v))
 
 
 def rendition_spec(spec):
-    """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2.
+    """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2; with
+    a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
-    of scale, max_dim, fit, stretch.  Values are not range-checked here: the engine fails a rendition
+    of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
+    to the edge) and cover (a (w, h) box: the largest centred part of the window with the box's aspect, at
+    the box's size).  Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
         raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
@@ -226,13 +262,25 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover)")
         fit = spec.get("fit")
         if fit is not None and not _is_pair(fit):
             raise ValueError(f"rendition {spec!r}: fit is not a (w, h) pair")
         fw, fh = (0, 0) if fit is None else (int(fit[0] or 0), int(fit[1] or 0))
-        return (int(spec.get("scale") or 0), int(spec.get("max_dim") or 0), fw, fh,
-                FIT_STRETCH if spec.get("stretch") else 0)
+        old = (int(spec.get("scale") or 0), int(spec.get("max_dim") or 0), fw, fh,
+               FIT_STRETCH if spec.get("stretch") else 0)
+        crop, cover = spec.get("crop"), spec.get("cover")
+        if crop is None and cover is None:
+            return old
+        if crop is not None and not _is_window(crop):
+            raise ValueError(f"rendition {spec!r}: crop is not an (x, y, w, h) window")
+        if cover is not None:
+            if not _is_pair(cover):
+                raise ValueError(f"rendition {spec!r}: cover is not a (w, h) pair")
+            if fit is not None:
+                raise ValueError(f"rendition {spec!r}: cover and fit both name a box")
+            old = old[:2] + (int(cover[0] or 0), int(cover[1] or 0), old[4] | FIT_COVER)
+        return old + ((0, 0, 0, 0) if crop is None else tuple(int(x or 0) for x in crop))
     raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
 
 
@@ -276,19 +324,81 @@ def _multi_cap(streams, per_item, floor):
     cap = 0
     for s, specs in zip(streams, per_item):
         full = max(floor, 4 * len(s))
-        for scale, max_dim, fw, fh, _ in specs:
+        for scale, max_dim, fw, fh, *_ in specs:
             plain_scale = 0 <= scale <= 3 and not (max_dim or fw or fh)
             cap += (full >> scale) + 65536 if plain_scale else full
     return cap
 
 
 def _multi_opts(per_item):
-    """(nrend int32[n], h2j_out_opts2[sum], total) of normalize_renditions' result."""
+    """(nrend int32[n], h2j_out_opts2[sum], total) of normalize_renditions' result; h2j_out_opts3[sum] when
+    a rendition names a window or a cover (the multi3 calls take those)."""
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    opts = (OutOpts2 * len(flat))(*[OutOpts2(a, b, w, h, f) for a, b, w, h, f in flat])
+    if any(len(t) > 5 for t in flat):
+        opts = (OutOpts3 * len(flat))(*[OutOpts3(*(tuple(t) + (0, 0, 0, 0))[:9]) for t in flat])
+    else:
+        opts = (OutOpts2 * len(flat))(*[OutOpts2(a, b, w, h, f) for a, b, w, h, f in flat])
     return nrend, opts, len(flat)
+
+
+def _per_item_shape(v, n, name, ok, what):
+    """v (None, one value for every item, or a per-item sequence of values or None) -> n values or None."""
+    if v is None:
+        return [None] * n
+    if ok(v):
+        return [tuple(v)] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"{name}: {len(v)} entries for {n} streams")
+    for p in v:
+        if p is not None and not ok(p):
+            raise ValueError(f"{name}: {p!r} is not {what}")
+    return [None if p is None else tuple(p) for p in v]
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover):
+    """Per-item rendition dicts of transcode()'s keywords when crop or cover is given."""
+    sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
+    ft = [None] * n if fit is None else _per_item_fit(fit, n)
+    if isinstance(stretch, (bool, np.bool_)) or stretch is None:
+        stf = [bool(stretch)] * n
+    else:
+        stf = [bool(x) for x in stretch]
+        if len(stf) != n:
+            raise ValueError(f"stretch: {len(stf)} entries for {n} streams")
+    cr = _per_item_shape(crop, n, "crop", _is_window, "an (x, y, w, h) window")
+    cv = _per_item_shape(cover, n, "cover", _is_pair, "a (w, h) pair")
+    out = []
+    for i in range(n):
+        d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
+        if ft[i] is not None and ft[i] != (0, 0):
+            d["fit"] = ft[i]
+        if cr[i] is not None:
+            d["crop"] = cr[i]
+        if cv[i] is not None:
+            d["cover"] = cv[i]
+        out.append([d])
+    return out
+
+
+def crop_window(w: int, h: int, crop=None, cover=None, scale: int = 0, max_dim: int = 0, fit=None,
+                stretch: bool = False):
+    """((x, y, w, h), (W_o, H_o)): the window and the output size of a cropped w x h picture for these
+    options -- include/h2j.h h2j_crop_window, the one place the window and cover rule lives.  ValueError
+    where the engine would fail the rendition (ERR_OUT_OPTS)."""
+    spec = {"scale": scale, "max_dim": max_dim, "stretch": stretch, "crop": (0, 0, 0, 0) if crop is None else crop}
+    if fit is not None:
+        spec["fit"] = fit
+    if cover is not None:
+        spec["cover"] = cover
+    o = OutOpts3(*rendition_spec(spec))
+    win, ow, oh = (ctypes.c_int32 * 4)(), ctypes.c_int(0), ctypes.c_int(0)
+    rc = load_library().h2j_crop_window(int(w), int(h), ctypes.byref(o), win, ctypes.byref(ow), ctypes.byref(oh))
+    if rc != 0:
+        raise ValueError(f"h2j_crop_window({w}, {h}, {spec!r}) failed ({rc})")
+    return tuple(int(x) for x in win), (ow.value, oh.value)
 
 
 def fit_size(w: int, h: int, fit, stretch: bool = False):
@@ -338,7 +448,7 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -349,10 +459,19 @@ class Engine:
         fit: exact-size output (h2j_out_opts2), a (w, h) box for every item or a per-item sequence
         of boxes or None; the JPEG is the largest even size inside the box with the aspect kept
         (fit_size), never larger than the picture; 0 / None leaves an axis unbounded.  stretch (a
-        bool or a per-item sequence): the box is the output size itself."""
+        bool or a per-item sequence): the box is the output size itself.
+
+        crop: the JPEG of a window of the picture (h2j_out_opts3), an (x, y, w, h) tuple in luma samples for
+        every item or a per-item sequence of windows or None; the other options act on the window.  cover: a
+        (w, h) box likewise: the largest centred part of the window (or picture) with the box's aspect, at
+        the box's size (crop_window has the rule)."""
         n = len(streams)
         if n == 0:
             return []
+        if crop is not None or cover is not None:  # one rendition per item through the multi3 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover))
+            self.last_status = [st[0] for st in self.last_status]
+            return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
         bufs = [_u8(s) for s in streams]
         ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
@@ -385,7 +504,7 @@ class Engine:
 
         renditions: one list of specs for every item, or one such list per item (normalize_renditions);
         a spec is an int (scale), a (w, h) tuple (fit) or a dict with any of scale, max_dim, fit,
-        stretch.  last_status has the result's shape.  out_cap: the output buffer size tried first
+        stretch, crop, cover (rendition_spec).  last_status has the result's shape.  out_cap: the output buffer size tried first
         (0: an estimate); renditions that did not fit (-50) make the call retry with a larger one."""
         n = len(streams)
         per_item = normalize_renditions(renditions, n)
@@ -400,7 +519,8 @@ class Engine:
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            rc = self._lib.h2j_engine_transcode_multi(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
+            call = self._lib.h2j_engine_transcode_multi3 if opts._type_ is OutOpts3 else self._lib.h2j_engine_transcode_multi
+            rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if not any(status[i] == -50 for i in range(total)):
                 break
             cap *= 4
@@ -423,8 +543,12 @@ class Engine:
         """transcode_multi for several batches through the asynchronous path, all submitted before the
         first wait; renditions as in transcode_multi, for every batch (per-item lists: one per item of
         each batch, so the batches then have the same length)."""
+        return self._multi_async(batches, [renditions] * len(batches))
+
+    def _multi_async(self, batches, renditions_of):
+        """transcode_multi_async with the renditions of each batch."""
         held, tickets = [], []
-        for streams in batches:
+        for streams, renditions in zip(batches, renditions_of):
             n = len(streams)
             per_item = normalize_renditions(renditions, n)
             nrend, opts, total = _multi_opts(per_item)
@@ -435,7 +559,8 @@ class Engine:
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
             held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item))
-            t = self._lib.h2j_engine_submit_multi(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
+            call = self._lib.h2j_engine_submit_multi3 if opts._type_ is OutOpts3 else self._lib.h2j_engine_submit_multi
+            t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if t <= 0:
                 raise RuntimeError(f"h2j_engine_submit_multi failed ({t})")
             tickets.append(t)
@@ -452,8 +577,11 @@ class Engine:
     def decode_multi(self, stream: bytes, renditions, pick: int):
         """(Y, U, V uint8 numpy, (W_o, H_o), mode): the 8-bit planes the JPEG stage reads for rendition
         `pick` of this picture with all of `renditions` (a list of specs) in flight; mode 0 unscaled,
-        1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi)."""
+        1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi).
+        Renditions with a crop or cover key go through decode_multi3."""
         specs = normalize_renditions([list(renditions)], 1)[0]
+        if any(len(t) > 5 for t in specs):
+            return self.decode_multi3(stream, renditions, pick)[:5]
         _, opts, total = _multi_opts([specs])
         buf = _u8(stream)
         cap = 8192 * 8192 * 3 // 2
@@ -465,6 +593,24 @@ class Engine:
             raise RuntimeError(f"h2j_engine_decode_multi failed ({rc}): {self.error()}")
         y, u, v, _ = self._planes(out, info)
         return y, u, v, (int(info[0]), int(info[1])), int(info[2])
+
+    def decode_multi3(self, stream: bytes, renditions, pick: int):
+        """decode_multi through h2j_engine_decode_multi3 (crop and cover), with the rendition's resolved
+        window: (Y, U, V, (W_o, H_o), mode, (x, y, w, h)).  Mode 5: the window has two or more K3s levels
+        among the renditions."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        total = len(specs)
+        opts = (OutOpts3 * total)(*[OutOpts3(*(tuple(t) + (0, 0, 0, 0))[:9]) for t in specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 8)()
+        rc = self._lib.h2j_engine_decode_multi3(self._h, buf, len(stream), total, opts, int(pick),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi3 failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8))
 
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
@@ -488,12 +634,27 @@ class Engine:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
     def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
-                        stretch=False) -> List[List[Optional[bytes]]]:
+                        stretch=False, crop=None, cover=None) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
         (each a scalar or a per-item sequence).  fit / stretch likewise: one (w, h) pair / bool for
-        every picture, or one entry per batch (each what transcode() takes)."""
+        every picture, or one entry per batch (each what transcode() takes).  crop / cover likewise: one
+        window / box for every picture, or one entry per batch."""
+        if crop is not None or cover is not None:
+            for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover))):
+                if v is not None and not one and len(v) != len(batches):
+                    raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
+            pick = lambda v, one, bi: v if v is None or one else v[bi]
+            rends = [_window_specs(len(streams),
+                                   pick(scale, isinstance(scale, (int, np.integer)), bi),
+                                   pick(max_dim, isinstance(max_dim, (int, np.integer)), bi),
+                                   pick(fit, _is_pair(fit), bi), pick(stretch, isinstance(stretch, (bool, np.bool_)), bi),
+                                   pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi))
+                     for bi, streams in enumerate(batches)]
+            res = self._multi_async(batches, rends)
+            self.last_status = [[st[0] for st in b] for b in self.last_status]
+            return [[o[0] for o in b] for b in res]
         for name, v, one in (("fit", fit, _is_pair(fit)), ("stretch", stretch, isinstance(stretch, (bool, np.bool_)))):
             if v is not None and not one and len(v) != len(batches):
                 raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")

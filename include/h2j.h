@@ -144,6 +144,46 @@ int64_t h2j_engine_submit_multi(h2j_engine *e, int n, const uint8_t *const *data
                                 const int32_t *nrend, const h2j_out_opts2 *opts, uint8_t *out, size_t out_cap,
                                 size_t *out_off, size_t *out_len, int *status);
 
+/* Crop and cover: the JPEG of a window of the picture (DESIGN.md "Crop and cover").  A rendition may name
+ * a window (crop_x, crop_y, crop_w, crop_h) in luma samples of the cropped W x H picture; its bytes are
+ * exactly those the call with the same remaining options returns for a picture whose cropped planes are
+ * the window's samples (luma rows y .. y+h-1, columns x .. x+w-1; chroma at half of each): scale_log2,
+ * max_dim and fit act on w x h, K3s clamps at the window's last column and row, SOF0 carries the output
+ * size.  crop_x, crop_y >= 0 and even; crop_w, crop_h >= 0 and even, 0: to the right / bottom edge
+ * (w = W - x, h = H - y; all four 0: the whole picture); the resolved w, h >= 2, x + w <= W, y + h <= H.
+ * Nothing is clamped: anything else fails that rendition alone with H2J_ERR_OUT_OPTS and a frame-error
+ * message that names the picture's size.
+ * H2J_FIT_COVER: the largest centred part of the window (the whole picture if none is named) with the
+ * aspect of the box fit_w x fit_h (both >= 2), sized as H2J_FIT_STRETCH sizes it -- a square thumbnail of
+ * a 16:9 picture.  Not with H2J_FIT_STRETCH, scale_log2 != 0 or max_dim != 0.  With box bw x bh, 64-bit
+ * products and flooring divisions: if w bh >= h bw: ch = h, cw = clamp(2 (h bw / (2 bh)), 2, w); else
+ * cw = w, ch = clamp(2 (w bh / (2 bw)), 2, h); x += 2 ((w - cw) / 4), y += 2 ((h - ch) / 4); the output
+ * is h2j_fit_size(cw, ch, bw, bh, H2J_FIT_STRETCH).  1920 x 1080, cover 256 x 256: window (420, 0, 1080,
+ * 1080), output 256 x 256.
+ * A window that resolves to the whole picture is not a window: the job is the h2j_out_opts2 one. */
+#define H2J_FIT_COVER 2
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts2; flags may hold H2J_FIT_COVER */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window; all 0: the whole picture */
+    int32_t reserved[3];                              /* must be 0 */
+} h2j_out_opts3;                                      /* 48 bytes */
+
+/* The window and size rule, a pure function (no engine, no GPU): for a cropped w x h picture (both even,
+ * 2..65536) and options o, win[0..3] = the resolved window x, y, w, h (after cover) and *ow x *oh = the
+ * output size (h2j_scaled_dim of the window at the resolved scale; h2j_fit_size of it; the cover size).
+ * Returns 0, or H2J_ERR_OUT_OPTS for invalid options or a window outside the picture (nothing is written). */
+int h2j_crop_window(int w, int h, const h2j_out_opts3 *o, int32_t *win, int *ow, int *oh);
+
+/* h2j_engine_transcode_multi / h2j_engine_submit_multi with h2j_out_opts3; an h2j_out_opts2 item is the
+ * h2j_out_opts3 item with the crop fields 0.  Renditions of one item that resolve to the same (window,
+ * output) are encoded once; two or more of the scales 1/2, 1/4, 1/8 of the same window come from one read. */
+int h2j_engine_transcode_multi3(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts3 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status);
+int64_t h2j_engine_submit_multi3(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                 const int32_t *nrend, const h2j_out_opts3 *opts, uint8_t *out, size_t out_cap,
+                                 size_t *out_off, size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -174,6 +214,10 @@ int h2j_engine_decode_resized(h2j_engine *e, const uint8_t *data, size_t size, i
  * mode 5: a K3s level written by K3p (the picture has two or more levels among its renditions). */
 int h2j_engine_decode_multi(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts2 *opts,
                             int pick, uint8_t *planes_out, size_t cap, int *info);
+/* The same with h2j_out_opts3; info has 8 entries: [4..7] = the rendition's resolved window x, y, w, h.
+ * Mode 5 then means: the window has two or more levels among the renditions (pyramids are per window). */
+int h2j_engine_decode_multi3(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts3 *opts,
+                             int pick, uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
@@ -214,6 +258,9 @@ int h2j_h265_to_jpeg_mem_fit(const uint8_t *data, size_t size, int fit_w, int fi
  * ran (per-rendition results in status), H2J_ERR_RENDITIONS for nrend outside 1..H2J_MAX_RENDITIONS. */
 int h2j_h265_to_jpeg_mem_multi(const uint8_t *data, size_t size, int nrend, const h2j_out_opts2 *opts, uint8_t **jpeg,
                                size_t *jpeg_len, int *status);
+/* the same with h2j_out_opts3 (crop and cover): concurrent callers with different windows still share GPU batches */
+int h2j_h265_to_jpeg_mem_multi3(const uint8_t *data, size_t size, int nrend, const h2j_out_opts3 *opts, uint8_t **jpeg,
+                                size_t *jpeg_len, int *status);
 void h2j_free(void *p);
 
 /* Library self-description (version, arch, build). */
