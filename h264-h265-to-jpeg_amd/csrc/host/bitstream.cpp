@@ -79,4 +79,61 @@ int detect_codec(const uint8_t* d, size_t n) {
     return 0;
 }
 
+int sei_display_orientation(const uint8_t* rbsp, size_t n, bool hevc, int cur) {
+    // [hor_flip][ver_flip][anticlockwise_rotation >> 14]: flip, then rotate anticlockwise, as an EXIF number
+    static const uint8_t kCode[2][2][4] = {{{0, 8, 3, 6}, {4, 7, 2, 5}}, {{2, 5, 4, 7}, {3, 6, 0, 8}}};
+    (void)hevc;  // the fields that differ (persistence / repetition period, extension) follow the ones read
+    size_t pos = 0;
+    while (n - pos >= 2) {  // a message has a type and a size byte at least; one byte left: the trailing bits
+        uint32_t type = 0, size = 0;
+        while (pos < n && rbsp[pos] == 0xFF && type < (1u << 20)) { type += 255; pos++; }
+        if (pos >= n) break;
+        type += rbsp[pos++];
+        while (pos < n && rbsp[pos] == 0xFF && size < (1u << 20)) { size += 255; pos++; }
+        if (pos >= n) {
+            if (type == 47) cur = 0;
+            break;
+        }
+        size += rbsp[pos++];
+        if (size > n - pos) {  // runs past the NAL
+            if (type == 47) cur = 0;
+            break;
+        }
+        if (type == 47) {
+            BitReader b(rbsp + pos, size);
+            if (b.u(1)) {
+                cur = 0;  // display_orientation_cancel_flag
+            } else {
+                const uint32_t hor = b.u(1), ver = b.u(1), rot = b.u(16);
+                cur = (size < 3 || (rot & 0x3FFF)) ? 0 : kCode[hor][ver][rot >> 14];
+            }
+        }
+        pos += size;
+    }
+    return cur;
+}
+
+int stream_display_orientation(const uint8_t* d, size_t n, int codec) {
+    std::vector<Nal> nals;
+    split_annexb(d, n, nals);
+    std::vector<uint8_t> rbsp;
+    int cur = 0;
+    for (const Nal& nal : nals) {
+        const size_t hdr = codec == 265 ? 2 : 1;
+        if (nal.n < hdr) continue;
+        const int type = codec == 265 ? (nal.p[0] >> 1) & 63 : nal.p[0] & 31;
+        if (codec == 265 ? type == 39 : type == 6) {
+            rbsp.resize(nal.n);
+            const size_t rn = unescape_rbsp(nal.p + hdr, nal.n - hdr, rbsp.data());
+            cur = sei_display_orientation(rbsp.data(), rn, codec == 265, cur);
+        } else if (codec == 265) {
+            // picture 0 starts at the first slice segment with first_slice_segment_in_pic_flag
+            if (type <= 21 && !(type >= 10 && type <= 15) && nal.n > 2 && (nal.p[2] & 0x80)) break;
+        } else if (type == 1 || type == 5) {
+            break;
+        }
+    }
+    return cur;
+}
+
 }  // namespace h2j

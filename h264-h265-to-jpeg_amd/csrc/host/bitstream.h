@@ -96,4 +96,13 @@ inline int ff_crop_left(int cl, int bps) {
 // h264/hevc probes (parameter-set NAL units with valid headers).
 int detect_codec(const uint8_t* d, size_t n);
 
+// The orientation (include/h2j.h: 0, 2..8) after the display orientation messages (payload type 47) of one
+// SEI RBSP, `cur` before it: the last message wins, a cancelled or unusable one (rotation no multiple of
+// 0x4000, truncated) gives 0.  Walks payload types and sizes with their 0xFF extension bytes, skips other
+// payloads by their size, stops at the RBSP trailing bits and never reads past n.  hevc: H.265 D.2.17
+// syntax, else H.264 D.1.27 (the same three fields lead both).
+int sei_display_orientation(const uint8_t* rbsp, size_t n, bool hevc, int cur);
+// The same for picture 0 of an Annex-B stream: the SEI NAL units in front of its first slice.  codec: 264 / 265
+int stream_display_orientation(const uint8_t* d, size_t n, int codec);
+
 }  // namespace h2j

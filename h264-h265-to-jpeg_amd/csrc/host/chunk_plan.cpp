@@ -58,14 +58,27 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
         // (MBAFF frames run on one workgroup: their K1 / deblocking walk macroblock pairs)
         f.k1bands = (f.codec == H2J_CODEC_H264 && f.ctb_h > kK1BandRows && !f.mbaff) ? (f.ctb_h + 15) / 16 : 1;
         f.xline = 0;
-        const size_t v0 = p.scaled.size(), w0 = p.wins.size();
+        const size_t v0 = p.scaled.size(), w0 = p.wins.size(), o0 = p.orients.size();
         p.vfirst[k] = static_cast<int>(v0);
-        auto source_of = [&](const FrameJob::Output& o) {  // the frame, or nf + the frame's window, added if new
-            if (!o.windowed) return k;
+        // the frame, or nf + the frame's window, added if new; an oriented output's window (the whole oriented
+        // picture is one) lies in the frame's oriented source of that orientation, added if new
+        auto source_of = [&](const FrameJob::Output& o) {
+            if (!o.windowed && !o.orient) return k;
+            int osrc = -1;
+            for (size_t i = o0; o.orient && i < p.orients.size(); i++)
+                if (p.orients[i].orient == o.orient) osrc = static_cast<int>(i);
+            if (o.orient && osrc < 0) {
+                h2j_orient rec{};
+                rec.frame = k;
+                rec.orient = o.orient;
+                p.orients.push_back(rec);
+                osrc = static_cast<int>(p.orients.size()) - 1;
+            }
             for (size_t w = w0; w < p.wins.size(); w++)
-                if (p.wins[w].x == o.win_x && p.wins[w].y == o.win_y && p.wins[w].w == o.win_w && p.wins[w].h == o.win_h)
+                if (p.wins[w].osrc == osrc && p.wins[w].x == o.win_x && p.wins[w].y == o.win_y && p.wins[w].w == o.win_w &&
+                    p.wins[w].h == o.win_h)
                     return p.nf + static_cast<int>(w);
-            p.wins.push_back(ChunkPlan::Window{k, o.win_x, o.win_y, o.win_w, o.win_h});
+            p.wins.push_back(ChunkPlan::Window{k, o.win_x, o.win_y, o.win_w, o.win_h, osrc});
             return p.nf + static_cast<int>(p.wins.size()) - 1;
         };
         auto view_of = [&](const FrameJob::Output& o) {  // the frame's view with this window and output, added if new
@@ -80,14 +93,14 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             sc.frame = k;
             sc.scale_log2 = o.scale_log2;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
-            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim(o.windowed ? o.win_w : f.out_w, sc.scale_log2);
-            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim(o.windowed ? o.win_h : f.out_h, sc.scale_log2);
+            sc.jpeg_w = resample ? o.fit_w : h2j_scaled_dim((o.windowed || o.orient) ? o.win_w : f.out_w, sc.scale_log2);
+            sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim((o.windowed || o.orient) ? o.win_h : f.out_h, sc.scale_log2);
             p.scaled.push_back(sc);
             p.vsrc.push_back(src);
             return static_cast<int>(p.scaled.size()) - 1;
         };
         for (int r = 0; r < j.nouts; r++)
-            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed) {
+            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed && !j.outs[r].orient) {
                 view_of(j.outs[r]);
                 break;
             }
@@ -118,7 +131,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     p.at.bytes = c.off;  // the maps follow (layout_maps)
 }
 
-// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
+// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][jcoef][res][aux]
 void layout_arena(ChunkPlan& p) {
     Cursor a;
     for (h2j_frame& f : p.frames) {
@@ -166,6 +179,18 @@ void layout_arena(ChunkPlan& p) {
             po += static_cast<size_t>(sc.spic_stride[c]) * ph;
         }
         sc.spic = a.take(po);
+    }
+    for (h2j_orient& rec : p.orients) {  // the oriented planes K3o writes, in the frame's sample type
+        const h2j_frame& f = p.frames[rec.frame];
+        const int pel = f.bit_depth > 8 ? 2 : 1;
+        const int ow = rec.orient >= 5 ? f.out_h : f.out_w, oh = rec.orient >= 5 ? f.out_w : f.out_h;
+        size_t po = 0;  // elements; every plane starts on a 64-byte boundary
+        for (int c = 0; c < 3; c++) {
+            rec.stride[c] = h2j_opic_stride(c ? ow / 2 : ow, pel);
+            rec.off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(rec.stride[c]) * (c ? oh / 2 : oh);
+        }
+        rec.opic = a.take(po * pel);
     }
     for (int v = 0; v < p.nv; v++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
         const h2j_scaled& sc = p.scaled[v];
@@ -321,6 +346,23 @@ void build_scale_classes(ChunkPlan& p) {
     }
 }
 
+// K3o map: the oriented sources by class (sample type x transposing), one launch per class present, its grid
+// as wide as the class's largest picture needs
+void build_orient_classes(ChunkPlan& p) {
+    for (int cls = 0; cls < H2J_ORIENT_CLASSES && !p.orients.empty(); cls++) {
+        p.orient_first[cls] = static_cast<int32_t>(p.orientmap.size());
+        for (const h2j_orient& rec : p.orients) {
+            const h2j_frame& f = p.frames[rec.frame];
+            const int pel = f.bit_depth > 8 ? 2 : 1;
+            const bool tr = rec.orient >= 5;
+            if (2 * (pel - 1) + (tr ? 1 : 0) != cls) continue;
+            p.orientmap.push_back(rec);
+            p.orient_count[cls]++;
+            p.orient_tiles[cls] = std::max(p.orient_tiles[cls], h2j_k3o_tiles(tr ? f.out_h : f.out_w, tr ? f.out_w : f.out_h, pel, tr));
+        }
+    }
+}
+
 // the maps' places in the staging buffer, behind the records; with scaled pictures or several
 // renditions of a frame the JPEG source views of all frames and the K3s / K3r / K3p maps follow
 void layout_maps(ChunkPlan& p) {
@@ -338,6 +380,8 @@ void layout_maps(ChunkPlan& p) {
     }
     p.at.pyr = c.off;
     if (!p.pyrmap.empty()) c.take(p.pyrmap.size() * sizeof(h2j_pyramid) + 16);
+    p.at.orient = c.off;  // only in chunks with oriented sources: every offset above is what it was
+    if (!p.orientmap.empty()) c.take(p.orientmap.size() * sizeof(h2j_orient) + 16);
     p.at.bytes = c.off;
 }
 
@@ -383,6 +427,13 @@ h2j_frame ChunkPlan::view(int v) const {
         f.out_w = w.out_w;
         f.out_h = w.out_h;
         f.pic = f.pic2;  // pic == pic2: K4a sums the window's MB variances (K3 SAO summed the whole picture's)
+        if (wins[vsrc[v] - nf].osrc >= 0) {  // ... of an oriented source: the oriented planes in place
+            f.pic = f.pic2 = w.pic2;
+            for (int c = 0; c < 3; c++) {
+                f.pic_stride[c] = w.pic_stride[c];
+                f.pic_off[c] = w.pic_off[c];
+            }
+        }
     }
     if (sc.scale_log2 == 0) return f;
     f.pic = f.pic2 = sc.spic;  // pic == pic2: K4a sums its MB variances (h2j_sao_folds_variance)
@@ -400,6 +451,15 @@ h2j_frame ChunkPlan::view(int v) const {
 h2j_frame ChunkPlan::wframe(int j) const {
     const Window& w = wins[j];
     h2j_frame f = frames[w.frame];
+    if (w.osrc >= 0) {  // the window lies in the oriented planes K3o wrote: pic == pic2, no conformance crop
+        const h2j_orient& rec = orients[w.osrc];
+        f.pic = f.pic2 = rec.opic;
+        f.crop_x = f.crop_y = 0;
+        for (int c = 0; c < 3; c++) {
+            f.pic_stride[c] = rec.stride[c];
+            f.pic_off[c] = rec.off[c];
+        }
+    }
     f.crop_x += w.x;
     f.crop_y += w.y;
     f.out_w = w.w;
@@ -415,6 +475,9 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     p.scaled.clear();
     p.vsrc.clear();
     p.wins.clear();
+    p.orients.clear();
+    p.orientmap.clear();
+    for (int cls = 0; cls < H2J_ORIENT_CLASSES; cls++) p.orient_first[cls] = p.orient_count[cls] = p.orient_tiles[cls] = 0;
     p.fstat.assign(static_cast<size_t>(p.nf), 0);
     p.rends.clear();
     p.scalemap.clear();
@@ -429,6 +492,7 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     build_k1_maps(p);
     build_sao_classes(p);
     build_scale_classes(p);
+    build_orient_classes(p);
     layout_maps(p);
     fill_descriptor(p);
 }

@@ -41,6 +41,7 @@ struct ChunkPlan {
     // A chunk without windows has none of this and uploads what it always did
     struct Window {
         int frame, x, y, w, h;  // the frame, and the window in luma samples of its cropped picture
+        int osrc;               // -1, or the oriented source (orients) the window lies in, in its coordinates
     };
     std::vector<Window> wins;  // the chunk's distinct windows, frame-major
     std::vector<int> vsrc;     // per view: the index the scale kernels find its source under -- its frame, or
@@ -52,7 +53,17 @@ struct ChunkPlan {
     int njstat = 0;            // jstat slots: nv, and one more per such frame
     h2j_frame wframe(int j) const;  // the frame copy of window j
 
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][jcoef][res][aux]
+    // Orientation (K3o): a distinct (frame, orientation) pair is an oriented source -- the frame's cropped
+    // planes, rotated or mirrored by K3o into an arena region of their own (opic; rows of whole 64-byte groups,
+    // planes on 64-byte boundaries, the frame's sample type).  Every output of an oriented picture is a window
+    // of it (the whole picture is the window 0, 0, W, H): its frame copy has pic == pic2 == opic, no
+    // conformance crop and the oriented strides, so K3s, K3r, K3p and K4 read it with the code they have.
+    // A chunk without oriented outputs has none of this and uploads what it always did
+    std::vector<h2j_orient> orients;    // the chunk's oriented sources, frame-major
+    std::vector<h2j_orient> orientmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_orient), uploaded
+    int32_t orient_first[H2J_ORIENT_CLASSES] = {0}, orient_count[H2J_ORIENT_CLASSES] = {0}, orient_tiles[H2J_ORIENT_CLASSES] = {0};
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
     size_t seg_cap = 0;  // payload pool bytes (K5)
     int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)
@@ -67,7 +78,7 @@ struct ChunkPlan {
     // staging layout: byte offset of each array in the one buffer the chunk uploads
     struct Staging {
         size_t frames = 0, tus = 0, coefs = 0, ctbs = 0, slices = 0, sl = 0, k1map = 0, k1all = 0, sao = 0, k1map8 = 0,
-               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, bytes = 0;
+               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, bytes = 0;
     } at;
 
     // the descriptor's scalar fields (counts, maxima, codec / sample-type masks, classes); its pointers,

@@ -42,6 +42,11 @@
 #include "job.h"
 #include "jpeg_writer.h"
 
+// the kernel library's orientation stage, null when the library in use is older than it (a weak reference:
+// bound when this library loads, so a stand-in or an older build selected beside it still loads)
+extern "C" int h2j_gpu_orient(const h2j_gpu_batch*, const h2j_orient*, const int32_t*, const int32_t*, const int32_t*, void*)
+    __attribute__((weak));
+
 namespace h2j {
 namespace {
 
@@ -176,25 +181,44 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
-// Output options: h2j_out_opts3 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
-// an h2j_out_opts2 item the crop fields)
-const h2j_out_opts3 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};  // the JPEG at the decoded size
-std::vector<h2j_out_opts3> opts3_of(int n, const h2j_out_opts* o) {  // o null: all plain
-    std::vector<h2j_out_opts3> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+// Output options: h2j_out_opts4 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
+// an h2j_out_opts2 item the crop fields, an h2j_out_opts3 item the orientation)
+const h2j_out_opts4 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};  // the JPEG at the decoded size
+std::vector<h2j_out_opts4> opts4_of(int n, const h2j_out_opts* o) {  // o null: all plain
+    std::vector<h2j_out_opts4> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
     for (int i = 0; o && i < n; i++) {
         v[i].scale_log2 = o[i].scale_log2;
         v[i].max_dim = o[i].max_dim;
     }
     return v;
 }
-h2j_out_opts3 opts3_of(const h2j_out_opts2& o) {
-    return h2j_out_opts3{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
+h2j_out_opts4 opts4_of(const h2j_out_opts3& o) {
+    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0,
+                         {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
 }
-std::vector<h2j_out_opts3> opts3_of(int n, const h2j_out_opts2* o) {
-    std::vector<h2j_out_opts3> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
-    for (int i = 0; o && i < n; i++) v[i] = opts3_of(o[i]);
+h2j_out_opts4 opts4_of(const h2j_out_opts2& o) {
+    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
+}
+template <typename T>
+std::vector<h2j_out_opts4> opts4_of(int n, const T* o) {  // h2j_out_opts2 / h2j_out_opts3 items
+    std::vector<h2j_out_opts4> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+    for (int i = 0; o && i < n; i++) v[i] = opts4_of(o[i]);
     return v;
 }
+// the h2j_out_opts4 items of a multi call's h2j_out_opts2 / h2j_out_opts3 items (valid counts)
+template <typename T>
+std::vector<h2j_out_opts4> multi_opts4(int n, const int32_t* nrend, const T* opts) {
+    int total = 0;
+    for (int i = 0; i < n; i++) total += nrend[i];
+    return opts4_of(total, opts);
+}
+bool reserved_zero(const h2j_out_opts4& o) { return std::all_of(o.reserved, o.reserved + 6, [](int32_t r) { return r == 0; }); }
+// the orientation (0, 2..8) the options name for a picture whose display orientation SEI says sei_orient
+int resolve_orient(const h2j_out_opts4& o, int sei_orient) {
+    const int r = o.orient == H2J_ORIENT_AUTO ? sei_orient : o.orient;
+    return r == 1 ? 0 : r;
+}
+const char kNoStageMessage[] = "the kernel library has no orientation stage (h2j_gpu_orient): oriented output needs a newer libh2j_hip.so";
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
 // max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does).
 // Exact-size output (h2j_out_opts2): the size h2j_fit_size gives.
@@ -204,9 +228,9 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
 }
 // what can be said of the options before the picture's size is known (an item none of whose renditions
 // passes is not parsed); the window's place in the picture is checked by resolve_output
-bool out_opts_valid(const h2j_out_opts3& o) {
+bool out_opts_valid(const h2j_out_opts4& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (o.reserved[0] || o.reserved[1] || o.reserved[2]) return false;
+    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8) return false;
     if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
     if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
         if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
@@ -215,7 +239,7 @@ bool out_opts_valid(const h2j_out_opts3& o) {
     if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts3& o, int w, int h) {
+int resolve_scale(const h2j_out_opts4& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
@@ -225,9 +249,13 @@ int resolve_scale(const h2j_out_opts3& o, int w, int h) {
 // window (include/h2j.h "Crop and cover"; error H2J_ERR_OUT_OPTS if it does not lie in the picture), then
 // what the remaining options make of a picture of the window's size.  A fit that resolves to the window's own
 // size is the unscaled output; one that K3s makes on all three planes (w = ow 2^k, h = oh 2^k: the
-// resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest
-FrameJob::Output resolve_output(const h2j_out_opts3& o, int W, int H) {
+// resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest.
+// Orientation (include/h2j.h "Orientation"; sei_orient: the picture's, for H2J_ORIENT_AUTO) comes first: the
+// rule runs on the oriented size, the window is in the oriented picture
+FrameJob::Output resolve_output(const h2j_out_opts4& o, int W, int H, int sei_orient) {
     FrameJob::Output out;
+    out.orient = resolve_orient(o, sei_orient);
+    if (out.orient >= 5) std::swap(W, H);
     int64_t x = o.crop_x, y = o.crop_y, w = o.crop_w ? o.crop_w : W - x, h = o.crop_h ? o.crop_h : H - y;
     if (w < 2 || h < 2 || x + w > W || y + h > H) {
         out.error = H2J_ERR_OUT_OPTS;
@@ -266,30 +294,37 @@ FrameJob::Output resolve_output(const h2j_out_opts3& o, int W, int H) {
 }
 // W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
 // message they always got
-std::string out_opts_message(const h2j_out_opts3& o, int W = 0, int H = 0) {
+std::string out_opts_message(const h2j_out_opts4& o, int W = 0, int H = 0, int sei_orient = 0) {
     std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
-           " (stretch needs a size), reserved " + ((o.reserved[0] || o.reserved[1] || o.reserved[2]) ? "non-zero" : "0");
-    if (!(o.crop_x || o.crop_y || o.crop_w || o.crop_h || (o.flags & H2J_FIT_COVER))) return m;
-    m += "; crop " + std::to_string(o.crop_x) + ", " + std::to_string(o.crop_y) + ", " + std::to_string(o.crop_w) + " x " +
-         std::to_string(o.crop_h) + " (even, >= 0, at least 2 x 2 inside the picture; cover needs a box and excludes stretch, scale_log2, max_dim)";
-    if (W > 0 && H > 0) m += "; the picture is " + std::to_string(W) + " x " + std::to_string(H);
+           " (stretch needs a size), reserved " + (reserved_zero(o) ? "0" : "non-zero");
+    const bool window = o.crop_x || o.crop_y || o.crop_w || o.crop_h || (o.flags & H2J_FIT_COVER);
+    if (window)
+        m += "; crop " + std::to_string(o.crop_x) + ", " + std::to_string(o.crop_y) + ", " + std::to_string(o.crop_w) + " x " +
+             std::to_string(o.crop_h) + " (even, >= 0, at least 2 x 2 inside the picture; cover needs a box and excludes stretch, scale_log2, max_dim)";
+    if (o.orient != 0) m += "; orient " + std::to_string(o.orient) + " (0..8, -1: the stream's display orientation)";
+    if (!(window && W > 0 && H > 0)) return m;
+    const int ro = (o.orient >= H2J_ORIENT_AUTO && o.orient <= 8) ? resolve_orient(o, sei_orient) : 0;
+    if (ro >= 5) std::swap(W, H);
+    m += "; the picture is " + std::to_string(W) + " x " + std::to_string(H);
+    if (ro) m += " at orientation " + std::to_string(ro);
     return m;
 }
 // the outputs of a parsed job: every rendition's is resolved on its own, and invalid options fail that
 // rendition alone
-void resolve_outputs(const h2j_out_opts3* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts4* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
-        if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h);
+        if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h, job.sei_orient);
         else job.outs[r].error = H2J_ERR_OUT_OPTS;
+        if (job.outs[r].error == 0 && job.outs[r].orient && !h2j_gpu_orient) job.outs[r].error = H2J_ERR_NO_STAGE;
     }
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts3* o, int nr, FrameJob& job, bool* ran) {
+int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts4* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -314,7 +349,7 @@ enum {
     EV_K1,
     EV_K2,
     EV_K3,
-    EV_SCALE,       // after K3s / K3r / K3p (scaled output)
+    EV_SCALE,       // after K3o (oriented output) and K3s / K3r / K3p (scaled output)
     EV_K4,
     EV_K5,          // the last kernel: the other slot's next chunk waits for it
     EV_STATS,       // after the stats D2H
@@ -367,7 +402,7 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3s + K3r + K3p
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3o + K3s + K3r + K3p
 // ST_RENDITIONS: JPEG outputs of the batch (ST_FRAMES: decoded pictures); ST_PARSED: pictures whose entropy decode ran
 
 struct ChunkTime {
@@ -386,7 +421,7 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts3> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    std::vector<h2j_out_opts4> opts;           // output options per rendition, item-major (a plain item has one rendition)
     std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
     int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
@@ -536,6 +571,7 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
         for (int v = 0; v < p.nv; v++) jv[v] = p.view(v);
         put(p.at.scale, p.scalemap.data(), p.scalemap.size() * sizeof(h2j_scaled));
         put(p.at.pyr, p.pyrmap.data(), p.pyrmap.size() * sizeof(h2j_pyramid));
+        put(p.at.orient, p.orientmap.data(), p.orientmap.size() * sizeof(h2j_orient));
     }
     const std::vector<FrameJob>& jobs = *s.jobs;
     auto pack = [&](int k) {  // the frame's record ranges are where plan_chunk numbered them
@@ -618,6 +654,11 @@ int Engine::launch(Slot& s, const Slot* after) {
     h2j_gpu_event_record(s.ev[EV_K2], st);
     if (s.stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K3], st);
+    // K3o: only in chunks with oriented sources (they exist only when the kernel library has the stage)
+    if (s.stages >= 3 && !p.orientmap.empty() &&
+        (!h2j_gpu_orient || h2j_gpu_orient(&b, reinterpret_cast<const h2j_orient*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.orient),
+                                           p.orient_first, p.orient_count, p.orient_tiles, st)))
+        return drain_fail(s, h2j_gpu_orient ? h2j_gpu_last_error() : kNoStageMessage);
     if (s.stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
     h2j_gpu_event_record(s.ev[EV_SCALE], st);
     if (s.stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
@@ -805,6 +846,13 @@ static double hbm_estimate(const FrameJob& j) {
                                                                : static_cast<double>(o.win_w) * o.win_h / (1 << 2 * o.scale_log2);
         est += 14.5 * opx + 8192;
     }
+    // oriented sources: the planes K3o writes, in the picture's sample type, once per distinct orientation
+    int oriented = 0;
+    for (int r = 0; r < j.nouts; r++)
+        if (j.outs[r].error == 0 && j.outs[r].orient && !((oriented >> j.outs[r].orient) & 1)) {
+            oriented |= 1 << j.outs[r].orient;
+            est += 1.5 * j.hdr.out_w * j.hdr.out_h * (j.hdr.bit_depth > 8 ? 2.0 : 1.0) + 4096;
+        }
     return est;
 }
 // JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
@@ -894,7 +942,8 @@ void Engine::drive_loop() {
                 for (int o = b->rbase[i]; o < b->rbase[i + 1]; o++) {
                     if (b->status[o] == 0) continue;
                     if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
-                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h);
+                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h, (*jobs)[i].sei_orient);
+                    else if (b->status[o] == H2J_ERR_NO_STAGE) b->msg[o] = kNoStageMessage;
                 }
             }
         if (b->jobset >= 0) jobset_busy[b->jobset] = false;
@@ -1112,7 +1161,7 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts3* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                             int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
@@ -1164,14 +1213,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::opts3_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::opts4_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts3_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts4_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1204,7 +1253,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts3_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts4_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1212,7 +1261,7 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts3_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts4_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1223,23 +1272,25 @@ static bool renditions_valid(int n, const int32_t* nrend, const void* opts) {
         if (nrend[i] < 1 || nrend[i] > H2J_MAX_RENDITIONS) return false;
     return true;
 }
-// the h2j_out_opts3 items of a multi call's h2j_out_opts2 items (valid counts)
-static std::vector<h2j_out_opts3> multi_opts3(int n, const int32_t* nrend, const h2j_out_opts2* opts) {
-    int total = 0;
-    for (int i = 0; i < n; i++) total += nrend[i];
-    return h2j::opts3_of(total, opts);
-}
 
 int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, multi_opts3(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
                                  const h2j_out_opts3* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                 int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+}
+
+int64_t h2j_engine_submit_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                 const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
@@ -1251,7 +1302,7 @@ int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data,
                                int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, multi_opts3(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1260,15 +1311,40 @@ int h2j_engine_transcode_multi3(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
     const int64_t t = submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
 int h2j_crop_window(int w, int h, const h2j_out_opts3* o, int32_t* win, int* ow, int* oh) {
-    if (!o || !win || !ow || !oh || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || !h2j::out_opts_valid(*o))
+    if (!o) return H2J_ERR_OUT_OPTS;
+    const h2j_out_opts4 o4 = h2j::opts4_of(*o);
+    int orient = 0;
+    return h2j_crop_window4(w, h, &o4, 0, win, ow, oh, &orient);
+}
+
+int h2j_stream_orientation(const uint8_t* data, size_t size) {
+    if (!data) return -1;
+    const int codec = h2j::detect_codec(data, size);
+    if (codec != 264 && codec != 265) return -100;
+    return h2j::stream_display_orientation(data, size, codec);
+}
+
+int h2j_crop_window4(int w, int h, const h2j_out_opts4* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
+    if (!o || !win || !ow || !oh || !orient || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
+        sei_orient > 8 || !h2j::out_opts_valid(*o))
         return H2J_ERR_OUT_OPTS;
-    const h2j::FrameJob::Output out = h2j::resolve_output(*o, w, h);
+    const h2j::FrameJob::Output out = h2j::resolve_output(*o, w, h, sei_orient == 1 ? 0 : sei_orient);
     if (out.error) return out.error;
+    *orient = out.orient;
     win[0] = out.win_x;
     win[1] = out.win_y;
     win[2] = out.win_w;
@@ -1301,7 +1377,7 @@ int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts3* o = &h2j::kPlainOutput, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts4* o = &h2j::kPlainOutput, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -1408,8 +1484,9 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts3* o, int nrend, int pick,
-                              uint8_t* planes_out, size_t cap, int* info, bool window_info = false) {
+// (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts4* o, int nrend, int pick,
+                              uint8_t* planes_out, size_t cap, int* info, int info_n = 4) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
     for (int r = 0; r < nrend; r++)
@@ -1419,8 +1496,11 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
         }
     if (single_job(w, data, size, o, nrend)) return -2;
     for (int r = 0; r < nrend; r++)
-        if (e.jobs[0].outs[r].error) {  // a window outside the picture
-            e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h));
+        if (e.jobs[0].outs[r].error == H2J_ERR_NO_STAGE) {
+            e.fail(h2j::kNoStageMessage);
+            return H2J_ERR_NO_STAGE;
+        } else if (e.jobs[0].outs[r].error) {  // a window outside the picture
+            e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h, e.jobs[0].sei_orient));
             return H2J_ERR_OUT_OPTS;
         }
     Slot& s = e.slot[0];
@@ -1439,18 +1519,23 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
     info[1] = h_;
     info[2] = (sc.scale_log2 >= 1 && sc.scale_log2 <= 3 && (levels & (levels - 1))) ? 5 : sc.scale_log2;
     info[3] = f.bit_depth;
-    if (window_info) {
-        const h2j::FrameJob::Output& wo = e.jobs[0].outs[pick];
+    const h2j::FrameJob::Output& wo = e.jobs[0].outs[pick];
+    if (info_n >= 8) {
         info[4] = wo.win_x;
         info[5] = wo.win_y;
         info[6] = wo.win_w;
         info[7] = wo.win_h;
     }
+    if (info_n >= 10) {
+        info[8] = wo.orient;
+        info[9] = e.jobs[0].sei_orient;
+    }
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
     size_t bytes = 0;  // the view's planes in the arena, from v.pic2
     for (int c = 0; c < 3; c++) {
-        const int rows = sc.scale_log2 ? (h_ >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
+        // (an unscaled oriented view lies in the oriented planes, whose rows end with the oriented picture's)
+        const int rows = sc.scale_log2 ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
         bytes = std::max(bytes, (static_cast<size_t>(v.pic_off[c]) + static_cast<size_t>(v.pic_stride[c]) * rows) * pel);
     }
     std::vector<uint8_t> tmp(bytes);
@@ -1474,13 +1559,13 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts3 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
+    const h2j_out_opts4 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts3 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, {0, 0, 0}};
+    const h2j_out_opts4 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
@@ -1488,14 +1573,21 @@ int h2j_engine_decode_multi(h2j_engine* w, const uint8_t* data, size_t size, int
                             uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts3_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
+    return decode_jpeg_source(w, data, size, h2j::opts4_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
 }
 
 int h2j_engine_decode_multi3(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (pick < 0 || pick >= nrend || !opts) return -1;
+    return decode_jpeg_source(w, data, size, h2j::opts4_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 8);
+}
+
+int h2j_engine_decode_multi4(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, int pick,
+                             uint8_t* planes_out, size_t cap, int* info) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend) return -1;
-    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, true);
+    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, 10);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

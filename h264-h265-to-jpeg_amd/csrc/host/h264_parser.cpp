@@ -1380,6 +1380,8 @@ int H264Parser::run(const uint8_t* data, size_t size, int threads) {
         } else if (type == 8) {
             if (have) break;
             if (parse_pps(b, pps_, sps_) < 0) { job_->message = "unsupported or invalid PPS"; return -3; }
+        } else if (type == 6) {  // SEI in front of picture 0: the display orientation
+            if (!have) job_->sei_orient = sei_display_orientation(rbsp_.data(), rn, false, job_->sei_orient);
         } else if (type == 1 || type == 5) {
             const uint32_t first_mb_u = b.ue();
             const int slice_type = static_cast<int>(b.ue());

@@ -2024,6 +2024,8 @@ int HevcParser::run(const uint8_t* data, size_t size, int threads) {
             prev = &sh_.back();
         } else if (type == 35 && have_pic) {
             break;
+        } else if (type == 39 && !have_pic) {  // PREFIX_SEI in front of picture 0: the display orientation
+            job_->sei_orient = sei_display_orientation(rbsp_.data(), rn, true, job_->sei_orient);
         }
     }
     if (!have_pic) { job_->message = "no picture found"; return -8; }

@@ -27,6 +27,9 @@ struct FrameJob {
     // the second field; the reference sends one packet (one field) and returns false (only
     // H2J_STRICT_REFERENCE acts on it)
     bool field_pair = false;
+    // the display orientation SEI in front of the picture's first slice as an orientation 0, 2..8
+    // (include/h2j.h "Orientation"; 0: none, cancelled or unusable).  Only H2J_ORIENT_AUTO acts on it
+    int sei_orient = 0;
     // the item's outputs, one per rendition it asks for (a plain item: one), resolved by the engine after
     // the parse from the rendition's options and the parsed size (resolve_output), or that rendition's own
     // error (invalid options fail it alone).  A job that did not parse has none
@@ -39,6 +42,9 @@ struct FrameJob {
         // output is the one without a window
         int win_x = 0, win_y = 0, win_w = 0, win_h = 0;
         bool windowed = false;
+        // the orientation of the picture the window lies in: 0 as decoded, 2..8 (include/h2j.h); the window
+        // is then in the coordinates of the oriented picture.  0: the job is the one without an orientation
+        int orient = 0;
     };
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;
@@ -55,6 +61,7 @@ struct FrameJob {
         message.clear();
         reorder_delay = false;
         field_pair = false;
+        sei_orient = 0;
         nouts = 0;
     }
 };

@@ -38,11 +38,21 @@ class OutOpts3(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 3)]
 
 
+class OutOpts4(ctypes.Structure):
+    """include/h2j.h h2j_out_opts4: h2j_out_opts3 and an orientation (rotate / flip on the GPU)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("orient", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
 FIT_COVER = 2  # include/h2j.h H2J_FIT_COVER
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
 MAX_RENDITIONS = 8  # include/h2j.h H2J_MAX_RENDITIONS: JPEG outputs of one item of a multi call
 ERR_RENDITIONS = -61  # include/h2j.h H2J_ERR_RENDITIONS: a rendition count outside 1..MAX_RENDITIONS
+ORIENT_AUTO = -1  # include/h2j.h H2J_ORIENT_AUTO: the orientation the stream's display orientation SEI names
+ERR_NO_STAGE = -62  # include/h2j.h H2J_ERR_NO_STAGE: an oriented rendition on a kernel library without the stage
 
 
 def lib_path() -> str:
@@ -148,6 +158,26 @@ def load_library() -> ctypes.CDLL:
         lib.h2j_crop_window.restype = ctypes.c_int
         lib.h2j_crop_window.argtypes = [ctypes.c_int, ctypes.c_int, opt3p, i32p, ctypes.POINTER(ctypes.c_int),
                                         ctypes.POINTER(ctypes.c_int)]
+    # orientation (rotate / flip): likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_multi4"):
+        opt4p = ctypes.POINTER(OutOpts4)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi4.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi4.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt4p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_multi4.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi4.argtypes = lib.h2j_engine_transcode_multi4.argtypes
+        lib.h2j_engine_decode_multi4.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi4.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt4p, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi4.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi4.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt4p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_crop_window4.restype = ctypes.c_int
+        lib.h2j_crop_window4.argtypes = [ctypes.c_int, ctypes.c_int, opt4p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_stream_orientation.restype = ctypes.c_int
+        lib.h2j_stream_orientation.argtypes = [u8p, ctypes.c_size_t]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -235,7 +265,16 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient")
+
+
+def _orient_value(v, what):
+    """An orientation as h2j_out_opts4 takes it: an int (0..8; the engine checks the range) or "auto"."""
+    if isinstance(v, str) and v == "auto":
+        return ORIENT_AUTO
+    if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+        return int(v)
+    raise ValueError(f'{what}: orient {v!r} is not an int (0..8) or "auto"')
 
 
 def _is_window(v):
@@ -246,12 +285,15 @@ def _is_window(v):
 
 def rendition_spec(spec):
     """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2; with
-    a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3.
+    a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3; with an orient
+    key those and orient: the fields of h2j_out_opts4.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
     of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
     to the edge) and cover (a (w, h) box: the largest centred part of the window with the box's aspect, at
-    the box's size).  Values are not range-checked here: the engine fails a rendition
+    the box's size) and orient (0..8, the EXIF orientation that makes the picture upright, or "auto": the one
+    the stream's display orientation SEI names; crop, cover, scale and fit then act on the oriented
+    picture).  Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
         raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
@@ -262,7 +304,7 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient)")
         fit = spec.get("fit")
         if fit is not None and not _is_pair(fit):
             raise ValueError(f"rendition {spec!r}: fit is not a (w, h) pair")
@@ -270,6 +312,10 @@ def rendition_spec(spec):
         old = (int(spec.get("scale") or 0), int(spec.get("max_dim") or 0), fw, fh,
                FIT_STRETCH if spec.get("stretch") else 0)
         crop, cover = spec.get("crop"), spec.get("cover")
+        if "orient" in spec:  # the h2j_out_opts4 fields, whatever else the spec names
+            rest = dict(spec)
+            orient = _orient_value(rest.pop("orient"), f"rendition {spec!r}")
+            return (tuple(rendition_spec(rest)) + (0, 0, 0, 0))[:9] + (orient,)
         if crop is None and cover is None:
             return old
         if crop is not None and not _is_window(crop):
@@ -336,7 +382,9 @@ def _multi_opts(per_item):
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    if any(len(t) > 5 for t in flat):
+    if any(len(t) > 9 for t in flat):  # an orientation: the multi4 calls
+        opts = (OutOpts4 * len(flat))(*[OutOpts4(*(tuple(t) + (0,) * 5)[:10]) for t in flat])
+    elif any(len(t) > 5 for t in flat):
         opts = (OutOpts3 * len(flat))(*[OutOpts3(*(tuple(t) + (0, 0, 0, 0))[:9]) for t in flat])
     else:
         opts = (OutOpts2 * len(flat))(*[OutOpts2(a, b, w, h, f) for a, b, w, h, f in flat])
@@ -358,8 +406,20 @@ def _per_item_shape(v, n, name, ok, what):
     return [None if p is None else tuple(p) for p in v]
 
 
-def _window_specs(n, scale, max_dim, fit, stretch, crop, cover):
-    """Per-item rendition dicts of transcode()'s keywords when crop or cover is given."""
+def _per_item_orient(orient, n):
+    """orient (None, one value for every item, or a per-item sequence of values or None) -> n values or None."""
+    if orient is None:
+        return [None] * n
+    if isinstance(orient, (str, int, np.integer)):
+        return [_orient_value(orient, "orient")] * n
+    v = list(orient)
+    if len(v) != n:
+        raise ValueError(f"orient: {len(v)} entries for {n} streams")
+    return [None if x is None else _orient_value(x, "orient") for x in v]
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None):
+    """Per-item rendition dicts of transcode()'s keywords when crop, cover or orient is given."""
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
     ft = [None] * n if fit is None else _per_item_fit(fit, n)
     if isinstance(stretch, (bool, np.bool_)) or stretch is None:
@@ -370,6 +430,7 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover):
             raise ValueError(f"stretch: {len(stf)} entries for {n} streams")
     cr = _per_item_shape(crop, n, "crop", _is_window, "an (x, y, w, h) window")
     cv = _per_item_shape(cover, n, "cover", _is_pair, "a (w, h) pair")
+    orr = _per_item_orient(orient, n)
     out = []
     for i in range(n):
         d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
@@ -379,15 +440,35 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover):
             d["crop"] = cr[i]
         if cv[i] is not None:
             d["cover"] = cv[i]
+        if orr[i] is not None:
+            d["orient"] = orr[i]
         out.append([d])
     return out
 
 
 def crop_window(w: int, h: int, crop=None, cover=None, scale: int = 0, max_dim: int = 0, fit=None,
-                stretch: bool = False):
+                stretch: bool = False, orient=0, sei_orient: int = 0):
     """((x, y, w, h), (W_o, H_o)): the window and the output size of a cropped w x h picture for these
     options -- include/h2j.h h2j_crop_window, the one place the window and cover rule lives.  ValueError
-    where the engine would fail the rendition (ERR_OUT_OPTS)."""
+    where the engine would fail the rendition (ERR_OUT_OPTS).
+
+    orient (0..8 or "auto", which resolves to sei_orient) other than 0: through h2j_crop_window4, for a decoded
+    w x h picture; the window and the size are those of the oriented picture and the resolved orientation
+    (0 or 2..8) follows them: ((x, y, w, h), (W_o, H_o), orientation)."""
+    if not (isinstance(orient, (int, np.integer)) and not isinstance(orient, (bool, np.bool_)) and orient == 0):
+        spec = {"scale": scale, "max_dim": max_dim, "stretch": stretch, "crop": (0, 0, 0, 0) if crop is None else crop,
+                "orient": orient}
+        if fit is not None:
+            spec["fit"] = fit
+        if cover is not None:
+            spec["cover"] = cover
+        o = OutOpts4(*rendition_spec(spec))
+        win, ow, oh, ro = (ctypes.c_int32 * 4)(), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        rc = load_library().h2j_crop_window4(int(w), int(h), ctypes.byref(o), int(sei_orient), win, ctypes.byref(ow),
+                                             ctypes.byref(oh), ctypes.byref(ro))
+        if rc != 0:
+            raise ValueError(f"h2j_crop_window4({w}, {h}, {spec!r}, {sei_orient}) failed ({rc})")
+        return tuple(int(x) for x in win), (ow.value, oh.value), ro.value
     spec = {"scale": scale, "max_dim": max_dim, "stretch": stretch, "crop": (0, 0, 0, 0) if crop is None else crop}
     if fit is not None:
         spec["fit"] = fit
@@ -399,6 +480,16 @@ def crop_window(w: int, h: int, crop=None, cover=None, scale: int = 0, max_dim: 
     if rc != 0:
         raise ValueError(f"h2j_crop_window({w}, {h}, {spec!r}) failed ({rc})")
     return tuple(int(x) for x in win), (ow.value, oh.value)
+
+
+def stream_orientation(stream: bytes) -> int:
+    """The display orientation (0, 2..8) of picture 0 of an Annex-B stream: what orient="auto" resolves to
+    (include/h2j.h h2j_stream_orientation; no entropy decode, no GPU).  ValueError for a stream that is neither
+    H.264 nor H.265."""
+    r = load_library().h2j_stream_orientation(_u8(stream), len(stream))
+    if r < 0:
+        raise ValueError(f"h2j_stream_orientation failed ({r}): not an H.264/H.265 Annex-B stream")
+    return r
 
 
 def fit_size(w: int, h: int, fit, stretch: bool = False):
@@ -448,7 +539,7 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False, crop=None, cover=None) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None, orient=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -464,12 +555,16 @@ class Engine:
         crop: the JPEG of a window of the picture (h2j_out_opts3), an (x, y, w, h) tuple in luma samples for
         every item or a per-item sequence of windows or None; the other options act on the window.  cover: a
         (w, h) box likewise: the largest centred part of the window (or picture) with the box's aspect, at
-        the box's size (crop_window has the rule)."""
+        the box's size (crop_window has the rule).
+
+        orient: the JPEG of the picture rotated / mirrored on the GPU (h2j_out_opts4): 0..8 (the EXIF
+        orientation that makes the picture upright) or "auto" (the stream's display orientation SEI), for every
+        item or a per-item sequence of values or None; every other option acts on the oriented picture."""
         n = len(streams)
         if n == 0:
             return []
-        if crop is not None or cover is not None:  # one rendition per item through the multi3 call
-            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover))
+        if crop is not None or cover is not None or orient is not None:  # one rendition per item through the multi3 / multi4 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient))
             self.last_status = [st[0] for st in self.last_status]
             return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
@@ -519,7 +614,8 @@ class Engine:
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            call = self._lib.h2j_engine_transcode_multi3 if opts._type_ is OutOpts3 else self._lib.h2j_engine_transcode_multi
+            call = {OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
+            call = getattr(self._lib, call)
             rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if not any(status[i] == -50 for i in range(total)):
                 break
@@ -559,7 +655,8 @@ class Engine:
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
             held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item))
-            call = self._lib.h2j_engine_submit_multi3 if opts._type_ is OutOpts3 else self._lib.h2j_engine_submit_multi
+            call = {OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
+            call = getattr(self._lib, call)
             t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if t <= 0:
                 raise RuntimeError(f"h2j_engine_submit_multi failed ({t})")
@@ -578,8 +675,10 @@ class Engine:
         """(Y, U, V uint8 numpy, (W_o, H_o), mode): the 8-bit planes the JPEG stage reads for rendition
         `pick` of this picture with all of `renditions` (a list of specs) in flight; mode 0 unscaled,
         1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi).
-        Renditions with a crop or cover key go through decode_multi3."""
+        Renditions with a crop or cover key go through decode_multi3, with an orient key through decode_multi4."""
         specs = normalize_renditions([list(renditions)], 1)[0]
+        if any(len(t) > 9 for t in specs):
+            return self.decode_multi4(stream, renditions, pick)[:5]
         if any(len(t) > 5 for t in specs):
             return self.decode_multi3(stream, renditions, pick)[:5]
         _, opts, total = _multi_opts([specs])
@@ -612,6 +711,26 @@ class Engine:
         y, u, v, _ = self._planes(out, info)
         return y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8))
 
+    def decode_multi4(self, stream: bytes, renditions, pick: int):
+        """decode_multi through h2j_engine_decode_multi4 (orientation): (Y, U, V, (W_o, H_o), mode, (x, y, w, h),
+        orientation, sei_orientation) -- the window in the oriented picture, the rendition's resolved
+        orientation (0 or 2..8) and the one the stream's display orientation SEI names.  At mode 0 the planes
+        of an oriented rendition are the oriented planes K3o wrote."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        total = len(specs)
+        opts = (OutOpts4 * total)(*[OutOpts4(*(tuple(t) + (0,) * 5)[:10]) for t in specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 10)()
+        rc = self._lib.h2j_engine_decode_multi4(self._h, buf, len(stream), total, opts, int(pick),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi4 failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
+                int(info[8]), int(info[9]))
+
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
         return self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
@@ -634,15 +753,17 @@ class Engine:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
     def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
-                        stretch=False, crop=None, cover=None) -> List[List[Optional[bytes]]]:
+                        stretch=False, crop=None, cover=None, orient=None) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
         (each a scalar or a per-item sequence).  fit / stretch likewise: one (w, h) pair / bool for
         every picture, or one entry per batch (each what transcode() takes).  crop / cover likewise: one
-        window / box for every picture, or one entry per batch."""
-        if crop is not None or cover is not None:
-            for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover))):
+        window / box for every picture, or one entry per batch; orient likewise: one value (0..8 or "auto")
+        for every picture, or one entry per batch."""
+        if crop is not None or cover is not None or orient is not None:
+            one_orient = isinstance(orient, (str, int, np.integer))
+            for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover)), ("orient", orient, one_orient)):
                 if v is not None and not one and len(v) != len(batches):
                     raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
             pick = lambda v, one, bi: v if v is None or one else v[bi]
@@ -650,7 +771,8 @@ class Engine:
                                    pick(scale, isinstance(scale, (int, np.integer)), bi),
                                    pick(max_dim, isinstance(max_dim, (int, np.integer)), bi),
                                    pick(fit, _is_pair(fit), bi), pick(stretch, isinstance(stretch, (bool, np.bool_)), bi),
-                                   pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi))
+                                   pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi),
+                                   pick(orient, one_orient, bi))
                      for bi, streams in enumerate(batches)]
             res = self._multi_async(batches, rends)
             self.last_status = [[st[0] for st in b] for b in self.last_status]

@@ -184,6 +184,54 @@ int64_t h2j_engine_submit_multi3(h2j_engine *e, int n, const uint8_t *const *dat
                                  const int32_t *nrend, const h2j_out_opts3 *opts, uint8_t *out, size_t out_cap,
                                  size_t *out_off, size_t *out_len, int *status);
 
+/* Orientation: the JPEG of the picture rotated or mirrored on the GPU (DESIGN.md "Orientation (K3o)").
+ * orient is 0..8: 0 and 1 mean "as decoded", 2..8 are the EXIF / TIFF orientation numbers, naming the
+ * transform that makes the picture upright.  For a cropped plane P (H rows x W columns, numpy notation;
+ * luma and both chroma planes alike) the oriented plane is
+ *   2: P[:, ::-1] mirror left-right   3: P[::-1, ::-1] 180 degrees   4: P[::-1, :] mirror top-bottom
+ *   5: P.T transpose   6: rot90(P, -1) 90 degrees clockwise   7: P[::-1, ::-1].T transverse
+ *   8: rot90(P, 1) 90 degrees anticlockwise            (5..8: the oriented picture is H x W)
+ * The oriented picture is the picture: the rendition's bytes are exactly those the same call with its
+ * remaining options returns for a picture whose cropped planes are the oriented planes.  crop is in luma
+ * samples of the oriented picture; cover, scale_log2, max_dim and fit act on it; SOF0 carries the
+ * oriented output size.  The stage permutes samples in their own type: no new arithmetic.
+ * H2J_ORIENT_AUTO: the orientation of the picture's display orientation SEI message (payload type 47,
+ * H.264 D.2.27 / H.265 D.3.17: flip, then rotate anticlockwise), the last such message in front of picture
+ * 0's first slice; 0 when there is none, when it is cancelled, malformed or truncated, or when its
+ * rotation is no multiple of 90 degrees.  The SEI is never applied unasked: every call without orient
+ * returns what it always returned.
+ * orient outside -1..8 or non-zero reserved: that rendition fails alone with H2J_ERR_OUT_OPTS. */
+#define H2J_ORIENT_AUTO (-1)
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts3 */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window of the oriented picture */
+    int32_t orient;                                   /* 0..8, or H2J_ORIENT_AUTO */
+    int32_t reserved[6];                              /* must be 0 */
+} h2j_out_opts4;                                      /* 64 bytes */
+/* status of an oriented rendition when the kernel library in use has no orientation stage (an older
+ * libh2j_hip.so selected beside this host library); the rendition fails alone */
+#define H2J_ERR_NO_STAGE (-62)
+
+/* The display orientation (0, 2..8) of picture 0 of an Annex-B stream of either codec, a pure function: it
+ * reads NAL headers and SEI messages only (no entropy decode).  Negative for a stream that is neither codec. */
+int h2j_stream_orientation(const uint8_t *data, size_t size);
+
+/* h2j_crop_window for a decoded w x h picture with an orientation: win[0..3] and *ow x *oh are in the
+ * coordinates of the oriented picture (h x w for orientations 5..8), *orient = the resolved orientation
+ * (0 or 2..8; sei_orient, 0..8, is what H2J_ORIENT_AUTO resolves to).  The one place the rule lives.
+ * Returns 0, or H2J_ERR_OUT_OPTS (nothing is written). */
+int h2j_crop_window4(int w, int h, const h2j_out_opts4 *o, int sei_orient, int32_t *win, int *ow, int *oh, int *orient);
+
+/* h2j_engine_transcode_multi3 / h2j_engine_submit_multi3 with h2j_out_opts4; an h2j_out_opts3 item is the
+ * h2j_out_opts4 item with orient 0.  Renditions of one item that resolve to the same (orientation, window,
+ * output) are encoded once; renditions with the same orientation share one pass of the orientation stage. */
+int h2j_engine_transcode_multi4(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts4 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status);
+int64_t h2j_engine_submit_multi4(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                 const int32_t *nrend, const h2j_out_opts4 *opts, uint8_t *out, size_t out_cap,
+                                 size_t *out_off, size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -218,13 +266,18 @@ int h2j_engine_decode_multi(h2j_engine *e, const uint8_t *data, size_t size, int
  * Mode 5 then means: the window has two or more levels among the renditions (pyramids are per window). */
 int h2j_engine_decode_multi3(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts3 *opts,
                              int pick, uint8_t *planes_out, size_t cap, int *info);
+/* The same with h2j_out_opts4; info has 10 entries: [0..7] as above with the window in the coordinates of the
+ * oriented picture, [8] = the rendition's resolved orientation (0 or 2..8), [9] = the picture's SEI orientation.
+ * At mode 0 the planes of an oriented rendition are the oriented planes K3o wrote, through K4's 8-bit conversion. */
+int h2j_engine_decode_multi4(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts4 *opts,
+                             int pick, uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
  * [9] frames  [10] algorithmic bytes of the GPU pixel path  [11] GPU entropy
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
- * h2j.py  [22] K3s / K3r / K3p scaled- and exact-size-output stage (GPU)  [23] renditions: JPEG outputs
+ * h2j.py  [22] K3o / K3s / K3r / K3p orientation, scaled- and exact-size-output stage (GPU)  [23] renditions: JPEG outputs
  * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran. */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
@@ -260,6 +313,9 @@ int h2j_h265_to_jpeg_mem_multi(const uint8_t *data, size_t size, int nrend, cons
                                size_t *jpeg_len, int *status);
 /* the same with h2j_out_opts3 (crop and cover): concurrent callers with different windows still share GPU batches */
 int h2j_h265_to_jpeg_mem_multi3(const uint8_t *data, size_t size, int nrend, const h2j_out_opts3 *opts, uint8_t **jpeg,
+                                size_t *jpeg_len, int *status);
+/* the same with h2j_out_opts4 (orientation): concurrent callers with different orientations still share GPU batches */
+int h2j_h265_to_jpeg_mem_multi4(const uint8_t *data, size_t size, int nrend, const h2j_out_opts4 *opts, uint8_t **jpeg,
                                 size_t *jpeg_len, int *status);
 void h2j_free(void *p);
 

@@ -88,6 +88,16 @@ constexpr int h2j_k3r_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) 
 constexpr int h2j_k3r_tiles(int jpeg_w, int jpeg_h) {
     return h2j_k3r_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3r_plane_tiles(jpeg_w / 2, jpeg_h / 2);
 }
+/* K3o (orientation): elements per row of an oriented plane of w samples of pel bytes: whole 64-byte groups */
+constexpr int h2j_opic_stride(int w, int pel) { return ((w * pel + 63) & ~63) / pel; }
+/* K3o workgroups (256 lanes) of one oriented ow x oh plane: mirrors move 256 16-byte row segments each,
+ * transposes one 64 x 64 tile each; and of a picture (three planes) */
+constexpr int h2j_k3o_plane_tiles(int ow, int oh, int pel, bool transposing) {
+    return transposing ? ((ow + 63) >> 6) * ((oh + 63) >> 6) : (((ow * pel + 15) >> 4) * oh + 255) >> 8;
+}
+constexpr int h2j_k3o_tiles(int ow, int oh, int pel, bool transposing) {
+    return h2j_k3o_plane_tiles(ow, oh, pel, transposing) + 2 * h2j_k3o_plane_tiles(ow / 2, oh / 2, pel, transposing);
+}
 /* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
  * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
@@ -195,6 +205,16 @@ int h2j_gpu_sao(const h2j_gpu_batch *b, void *stream);
  * pictures of the same map, and K3p: every K3s level of the pictures of b->pyr_map from one read;
  * no launch when the batch has none */
 int h2j_gpu_scale(const h2j_gpu_batch *b, void *stream);
+/* K3o: the oriented sources (h2j_orient, a device array), grouped by class (2 * (sample type: 0 8-bit, 1 high
+ * bit depth) + (transposing: orientations 5..8)): cropped frame.pic2 -> the planes at h2j_orient.opic, rotated
+ * or mirrored, in the frame's sample type.  first / count / tiles: per class (host arrays of
+ * H2J_ORIENT_CLASSES), tiles the most workgroups one picture of the class needs (h2j_k3o_tiles); one launch
+ * per class present.  Runs after K3 SAO and before h2j_gpu_scale, whose kernels read the oriented planes
+ * through frame copies.  A kernel library older than the stage lacks the symbol: the host library resolves it
+ * when it loads and fails oriented renditions alone (H2J_ERR_NO_STAGE) */
+#define H2J_ORIENT_CLASSES 4
+int h2j_gpu_orient(const h2j_gpu_batch *b, const h2j_orient *map, const int32_t *first, const int32_t *count,
+                   const int32_t *tiles, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat
  * (variance, rate control, FDCT + quantiser + zigzag, symbol histograms) */

@@ -156,6 +156,18 @@ typedef struct {
     h2j_scaled lvl[3];              /* [k - 1]: the level-k output (valid where mask has bit k) */
 } h2j_pyramid;
 
+/* One oriented source of a batch (DESIGN.md "Orientation (K3o)"): K3o reads the cropped pic2 of frame
+ * `frame` and writes its three planes, rotated or mirrored as `orient` says (2..8, the EXIF numbers:
+ * include/h2j.h), in the frame's own sample type at opic.  The K3s / K3r / K3p kernels and K4 read that
+ * picture through a copy of the frame behind the batch's real frames, as they read a window. */
+typedef struct {
+    int32_t frame;                  /* index of the picture in the batch's frames */
+    int32_t orient;                 /* 2..8 */
+    uint64_t opic;                  /* oriented planes (arena offset, bytes; 256-byte aligned) */
+    int32_t stride[3];              /* elements per row of each oriented plane (whole 64-byte groups) */
+    int32_t off[3];                 /* element offset of each oriented plane inside opic (64-byte aligned) */
+} h2j_orient;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;
