@@ -5158,12 +5158,20 @@ __constant__ uint8_t kZigzag[64] = {
 
 // Rate control of FFmpeg's one-pass RC for frame 0; IEEE
 // double with correctly rounded sqrt/div and no contraction, as on the host.
-__global__ void __launch_bounds__(64) h2j_k4b_ratecontrol(const h2j_frame* frames, uint8_t* arena) {
+// qforce (may be null): per view, 0 or the quantiser scale 2..31 the caller sets (h2j_gpu_jpeg2): the formula is
+// skipped, the matrix and the quantiser are those of that scale
+__global__ void __launch_bounds__(64) h2j_k4b_ratecontrol(const h2j_frame* frames, uint8_t* arena, const int32_t* qforce) {
 #pragma clang fp contract(off)
     const h2j_frame& f = frames[blockIdx.x];
     h2j_jstat* js = reinterpret_cast<h2j_jstat*>(arena + f.jstat);
     __shared__ int qs_sh;
-    if (threadIdx.x == 0) {
+    const int forced = qforce ? qforce[blockIdx.x] : 0;  // uniform
+    if (threadIdx.x == 0 && forced) {
+        const int qscale = forced < 2 ? 2 : (forced > 31 ? 31 : forced);
+        js->qscale = qscale;
+        js->lambda = qscale * 118;
+        qs_sh = qscale;
+    } else if (threadIdx.x == 0) {
         const double qp2l = 118.0, qs = 2.0 * 118.0;
         const long long V = js->var_sum;
         const int T = static_cast<int>(qp2l * 7.0 * __dsqrt_rn(static_cast<double>(V)) / qs);
@@ -5924,7 +5932,9 @@ int h2j_gpu_scale(const h2j_gpu_batch* b, void* stream) {
     return 0;
 }
 
-int h2j_gpu_jpeg(const h2j_gpu_batch* b, void* stream) {
+int h2j_gpu_jpeg(const h2j_gpu_batch* b, void* stream) { return h2j_gpu_jpeg2(b, nullptr, stream); }
+
+int h2j_gpu_jpeg2(const h2j_gpu_batch* b, const int32_t* qforce, void* stream) {
     if (!b || b->nframes <= 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const h2j_frame* jf = b->jframes ? b->jframes : b->frames;  // JPEG source views
@@ -5935,7 +5945,7 @@ int h2j_gpu_jpeg(const h2j_gpu_batch* b, void* stream) {
         if (r) return r;
     }
     int r = 0;
-    hipLaunchKernelGGL(h2j_k4b_ratecontrol, dim3(b->nframes), dim3(64), 0, s, jf, b->arena);
+    hipLaunchKernelGGL(h2j_k4b_ratecontrol, dim3(b->nframes), dim3(64), 0, s, jf, b->arena, qforce);
     r = check(hipGetLastError(), "h2j_k4b_ratecontrol");
     if (r) return r;
     const int nblk = mbs * 6;

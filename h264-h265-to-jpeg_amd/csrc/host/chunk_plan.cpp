@@ -85,7 +85,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             const int src = source_of(o);
             for (size_t v = v0; v < p.scaled.size(); v++) {
                 const h2j_scaled& sv = p.scaled[v];
-                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 &&
+                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && p.vqscale[v] == o.qscale && p.vsharpen[v] == o.sharpen &&
                     (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
                     return static_cast<int>(v);
             }
@@ -97,10 +97,14 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim((o.windowed || o.orient) ? o.win_h : f.out_h, sc.scale_log2);
             p.scaled.push_back(sc);
             p.vsrc.push_back(src);
+            p.vqscale.push_back(o.qscale);
+            p.vsharpen.push_back(o.sharpen);
+            p.qforced = p.qforced || o.qscale != 0;
             return static_cast<int>(p.scaled.size()) - 1;
         };
         for (int r = 0; r < j.nouts; r++)
-            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed && !j.outs[r].orient) {
+            if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed && !j.outs[r].orient && !j.outs[r].qscale &&
+                !j.outs[r].sharpen) {
                 view_of(j.outs[r]);
                 break;
             }
@@ -191,6 +195,25 @@ void layout_arena(ChunkPlan& p) {
             po += static_cast<size_t>(rec.stride[c]) * (c ? oh / 2 : oh);
         }
         rec.opic = a.take(po * pel);
+    }
+    for (int v = 0; v < p.nv; v++) {  // the 8-bit sharpened planes K3u writes and K4 reads (sharpened views only)
+        p.vfin[v] = -1;
+        if (!p.vsharpen[v]) continue;
+        const h2j_scaled& sc = p.scaled[v];
+        h2j_finish rec{};
+        rec.w = sc.jpeg_w;
+        rec.h = sc.jpeg_h;
+        rec.sharpen = p.vsharpen[v];
+        rec.jstat = sc.jstat;
+        size_t po = 0;
+        for (int c = 0; c < 3; c++) {
+            rec.dst_stride[c] = h2j_spic_stride(c ? rec.w / 2 : rec.w);
+            rec.dst_off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(rec.dst_stride[c]) * (c ? rec.h / 2 : rec.h);
+        }
+        rec.dst = a.take(po);
+        p.vfin[v] = static_cast<int>(p.fins.size());
+        p.fins.push_back(rec);
     }
     for (int v = 0; v < p.nv; v++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
         const h2j_scaled& sc = p.scaled[v];
@@ -310,6 +333,15 @@ void build_scale_classes(ChunkPlan& p) {
         if (levels[k] & (levels[k] - 1)) npyr++;
         else levels[k] = 0;  // one level: K3s
     }
+    // a pyramid writes one view a level: the source's first at that level.  Later views of the same source and
+    // level -- they differ from it in qscale or sharpen only -- have planes of their own, written by K3s
+    auto in_pyramid = [&](int v) {
+        const h2j_scaled& sc = p.scaled[v];
+        if (!k3s_level(sc) || !((levels[p.vsrc[v]] >> sc.scale_log2) & 1)) return false;
+        for (int u = p.vfirst[sc.frame]; u < v; u++)
+            if (p.vsrc[u] == p.vsrc[v] && p.scaled[u].scale_log2 == sc.scale_log2) return false;
+        return true;
+    };
     for (int cls = 0; cls < H2J_PYR_CLASSES && npyr; cls++) {
         d.pyr_first[cls] = static_cast<int>(p.pyrmap.size());
         for (int k = 0; k < ns; k++) {
@@ -321,7 +353,7 @@ void build_scale_classes(ChunkPlan& p) {
             py.frame = k;
             py.mask = levels[k];
             for (int v = p.vfirst[fr]; v < p.vfirst[fr + 1]; v++)
-                if (k3s_level(p.scaled[v]) && p.vsrc[v] == k) {
+                if (p.vsrc[v] == k && in_pyramid(v)) {
                     py.lvl[p.scaled[v].scale_log2 - 1] = p.scaled[v];
                     py.lvl[p.scaled[v].scale_log2 - 1].frame = k;
                 }
@@ -334,7 +366,7 @@ void build_scale_classes(ChunkPlan& p) {
         d.scale_first[cls] = static_cast<int>(p.scalemap.size());
         for (int v = 0; v < p.nv; v++) {
             const h2j_scaled& sc = p.scaled[v];
-            if (sc.scale_log2 == 0 || (levels[p.vsrc[v]] >> sc.scale_log2) & 1) continue;  // unscaled, or K3p's
+            if (sc.scale_log2 == 0 || in_pyramid(v)) continue;  // unscaled, or K3p's
             const int hbd = p.frames[sc.frame].bit_depth > 8 ? 1 : 0;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
             if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
@@ -363,6 +395,36 @@ void build_orient_classes(ChunkPlan& p) {
     }
 }
 
+// K3u map: the sharpened outputs with their sources (what each view is without its sharpening), by source class
+// (0: the 8-bit planes K3s / K3r / K3p wrote; 1: another 8-bit source; 2: a 16-bit source), one launch per class
+// present, its grid as wide as the class's largest output needs
+void build_finish_classes(ChunkPlan& p) {
+    for (int v = 0; v < p.nv; v++) {
+        if (p.vfin[v] < 0) continue;
+        h2j_finish& rec = p.fins[p.vfin[v]];
+        const h2j_frame src = p.base_view(v);
+        rec.bit_depth = src.bit_depth;
+        rec.bit_depth_c = src.bit_depth_c;
+        rec.crop_x = src.crop_x;
+        rec.crop_y = src.crop_y;
+        rec.wide = p.scaled[v].scale_log2 != 0 ? 1 : 0;
+        rec.src = src.pic2;
+        for (int c = 0; c < 3; c++) {
+            rec.src_stride[c] = src.pic_stride[c];
+            rec.src_off[c] = src.pic_off[c];
+        }
+    }
+    for (int cls = 0; cls < H2J_FINISH_CLASSES && !p.fins.empty(); cls++) {
+        p.fin_first[cls] = static_cast<int32_t>(p.finmap.size());
+        for (const h2j_finish& rec : p.fins) {
+            if ((rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1) != cls) continue;
+            p.finmap.push_back(rec);
+            p.fin_count[cls]++;
+            p.fin_tiles[cls] = std::max(p.fin_tiles[cls], h2j_k3u_tiles(rec.w, rec.h));
+        }
+    }
+}
+
 // the maps' places in the staging buffer, behind the records; with scaled pictures or several
 // renditions of a frame the JPEG source views of all frames and the K3s / K3r / K3p maps follow
 void layout_maps(ChunkPlan& p) {
@@ -382,6 +444,10 @@ void layout_maps(ChunkPlan& p) {
     if (!p.pyrmap.empty()) c.take(p.pyrmap.size() * sizeof(h2j_pyramid) + 16);
     p.at.orient = c.off;  // only in chunks with oriented sources: every offset above is what it was
     if (!p.orientmap.empty()) c.take(p.orientmap.size() * sizeof(h2j_orient) + 16);
+    p.at.finish = c.off;  // only in chunks with sharpened outputs, and
+    if (!p.finmap.empty()) c.take(p.finmap.size() * sizeof(h2j_finish) + 16);
+    p.at.qforce = c.off;  // only in chunks with a forced quantiser scale: one int32 a view
+    if (p.qforced) c.take(static_cast<size_t>(p.nv) * 4 + 16);
     p.at.bytes = c.off;
 }
 
@@ -405,9 +471,9 @@ void fill_descriptor(ChunkPlan& p) {
     d.k1hevc_n = static_cast<int32_t>(p.k1hevc.size());
     // pictures whose MB variances K4a sums (K3 sums the others'; no K4a launch when none is left)
     // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
-    // (a window: always K4a, on the window)
+    // (a window: always K4a, on the window; a sharpened view: always K4a, on the sharpened planes)
     for (int v = 0; v < p.nv; v++)
-        d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf) ? 0 : 1;
+        d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v]) ? 0 : 1;
 }
 
 }  // namespace
@@ -415,7 +481,25 @@ void fill_descriptor(ChunkPlan& p) {
 // An unscaled frame is its own view; a scaled frame's view is the 8-bit picture K3s, K3r or K3p writes
 // at its h2j_scaled record's spic (include/h2j_gpu.h h2j_gpu_batch.jframes).  Every view has its own
 // jcoef / tile region and jstat (the first view keeps the frame's own).
+// A sharpened view is the 8-bit picture K3u writes at its h2j_finish record's dst, from what the view is without
+// the sharpening (base_view)
 h2j_frame ChunkPlan::view(int v) const {
+    h2j_frame f = base_view(v);
+    if (vfin[v] < 0) return f;
+    const h2j_finish& rec = fins[vfin[v]];
+    f.pic = f.pic2 = rec.dst;  // pic == pic2: K4a sums the sharpened picture's MB variances
+    f.crop_x = f.crop_y = 0;
+    f.out_w = rec.w;
+    f.out_h = rec.h;
+    f.bit_depth = f.bit_depth_c = 8;
+    for (int c = 0; c < 3; c++) {
+        f.pic_stride[c] = rec.dst_stride[c];
+        f.pic_off[c] = rec.dst_off[c];
+    }
+    return f;
+}
+
+h2j_frame ChunkPlan::base_view(int v) const {
     const h2j_scaled& sc = scaled[v];
     h2j_frame f = frames[sc.frame];
     f.jcoef = vjcoef[v];
@@ -478,6 +562,11 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     p.orients.clear();
     p.orientmap.clear();
     for (int cls = 0; cls < H2J_ORIENT_CLASSES; cls++) p.orient_first[cls] = p.orient_count[cls] = p.orient_tiles[cls] = 0;
+    for (auto* m : {&p.fins, &p.finmap}) m->clear();
+    p.vqscale.clear();
+    p.vsharpen.clear();
+    p.qforced = false;
+    for (int cls = 0; cls < H2J_FINISH_CLASSES; cls++) p.fin_first[cls] = p.fin_count[cls] = p.fin_tiles[cls] = 0;
     p.fstat.assign(static_cast<size_t>(p.nf), 0);
     p.rends.clear();
     p.scalemap.clear();
@@ -486,13 +575,16 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     std::memset(&p.desc, 0, sizeof(p.desc));
     number_frames_and_views(jobs, live, p);
     // scaled pictures present, or several renditions of a frame: a views array is uploaded
-    p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; });
+    p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; }) ||
+              std::any_of(p.vsharpen.begin(), p.vsharpen.end(), [](int a) { return a != 0; });  // ... or a sharpened view
     p.vjcoef.resize(static_cast<size_t>(p.nv));
+    p.vfin.assign(static_cast<size_t>(p.nv), -1);
     layout_arena(p);
     build_k1_maps(p);
     build_sao_classes(p);
     build_scale_classes(p);
     build_orient_classes(p);
+    build_finish_classes(p);
     layout_maps(p);
     fill_descriptor(p);
 }

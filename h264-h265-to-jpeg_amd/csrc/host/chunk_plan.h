@@ -21,7 +21,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct ChunkPlan {
     // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
-    // is (frame, window, resolved output) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
+    // is (frame, window, resolved output, qscale, sharpen) with its own h2j_scaled, scaled planes, jcoef / tile region and jstat;
     // the first view of a frame -- its unscaled rendition if it has one -- keeps the frame's own jcoef
     // and jstat.  One rendition per item: nv == nf, view k is frame k
     int nf = 0, nv = 0;
@@ -63,7 +63,23 @@ struct ChunkPlan {
     std::vector<h2j_orient> orientmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_orient), uploaded
     int32_t orient_first[H2J_ORIENT_CLASSES] = {0}, orient_count[H2J_ORIENT_CLASSES] = {0}, orient_tiles[H2J_ORIENT_CLASSES] = {0};
 
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][jcoef][res][aux]
+    // Finishing (K3u, forced qscale): a view is (frame, window, resolved output, qscale, sharpen).  Views that differ
+    // only in qscale or sharpen share nothing: each has its scaled planes and runs the scale stage for itself (of
+    // two views at one K3s level of a pyramid, K3p writes the first and K3s the others).  A sharpened view has a
+    // record: K3u reads what the view would be without sharpening (base_view) and writes 8-bit planes of its own
+    // (upic; the spic strides), which view() then shows with pic == pic2.  The views' forced scales are uploaded
+    // (one int32 a view) only by chunks that force one.  A chunk without finishing has none of this and uploads
+    // what it always did
+    std::vector<int32_t> vqscale;    // per view: the quantiser scale K4b is to use, 0: the rate control's
+    std::vector<int> vsharpen;       // per view: the unsharp mask's strength, 0: none
+    std::vector<int> vfin;           // per view: -1, or its record in fins
+    std::vector<h2j_finish> fins;    // the chunk's sharpened outputs, view-major
+    std::vector<h2j_finish> finmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_finish), uploaded
+    int32_t fin_first[H2J_FINISH_CLASSES] = {0}, fin_count[H2J_FINISH_CLASSES] = {0}, fin_tiles[H2J_FINISH_CLASSES] = {0};
+    bool qforced = false;            // a view of the chunk forces its quantiser scale
+    h2j_frame base_view(int v) const;  // view v without its sharpening: what K3u reads
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
     size_t seg_cap = 0;  // payload pool bytes (K5)
     int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)
@@ -78,7 +94,7 @@ struct ChunkPlan {
     // staging layout: byte offset of each array in the one buffer the chunk uploads
     struct Staging {
         size_t frames = 0, tus = 0, coefs = 0, ctbs = 0, slices = 0, sl = 0, k1map = 0, k1all = 0, sao = 0, k1map8 = 0,
-               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, bytes = 0;
+               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, finish = 0, qforce = 0, bytes = 0;
     } at;
 
     // the descriptor's scalar fields (counts, maxima, codec / sample-type masks, classes); its pointers,

@@ -24,6 +24,7 @@
 
 #include "IDecoder.h"
 #include "h2j.h"
+#include "job.h"
 
 void LOG(const char* format, ...) {
     char log[1024] = {0};
@@ -54,8 +55,8 @@ struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
     // the options of the picture's renditions: one (all 0: the decoded size; h2j_h265_to_jpeg_mem_scaled,
-    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3, _multi4); per rendition the JPEG and status once the batch ran
-    std::vector<h2j_out_opts4> opts{h2j_out_opts4{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}}};
+    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3, _multi4, _multi5); per rendition the JPEG and status once the batch ran
+    std::vector<h2j_out_opts5> opts{h2j_out_opts5{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}}};
     std::vector<std::vector<uint8_t>> jpegs;
     std::vector<int> rstatus;
     int status = 0;  // of the first rendition, which is all a plain caller asks for (-1: the batch did not run)
@@ -114,7 +115,7 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
 }
 
 // run one batch (caller holds no lock); fills jpegs / rstatus / status / error of each request.  Every
-// picture is decoded once (h2j_engine_transcode_multi4; a plain request is an item with one rendition)
+// picture is decoded once (h2j_engine_transcode_multi5; a plain request is an item with one rendition)
 void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
     if (n == 0) return;
@@ -122,7 +123,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<size_t> sizes(n);
     std::vector<int32_t> nrend(n);
     std::vector<int> base(n + 1, 0);
-    std::vector<h2j_out_opts4> opts;
+    std::vector<h2j_out_opts5> opts;
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
         const Request* q = batch[i];
@@ -140,7 +141,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = h2j_engine_transcode_multi4(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
+        r = h2j_engine_transcode_multi5(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
                                        len.data(), status.data());
         bool small = false;
         for (int i = 0; i < total; i++) small = small || status[i] == -50;
@@ -280,13 +281,14 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
 }
 
-static h2j_out_opts4 opts4_of(const h2j_out_opts3& o) {
-    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0,
-                         {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
+static h2j_out_opts5 opts5_of(const h2j_out_opts3& o) {
+    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0,
+                         {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
 }
-static h2j_out_opts4 opts4_of(const h2j_out_opts2& o) {
-    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
+static h2j_out_opts5 opts5_of(const h2j_out_opts2& o) {
+    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
 }
+static h2j_out_opts5 opts5_of(const h2j_out_opts4& o) { return h2j::widen_opts4(o); }
 
 static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& opts, uint8_t** jpeg, size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
@@ -296,7 +298,7 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts[0] = opts4_of(opts);
+    req.opts[0] = opts5_of(opts);
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -324,21 +326,30 @@ extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int 
                                           size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    std::vector<h2j_out_opts4> o4;
-    for (int r = 0; r < nrend; r++) o4.push_back(opts4_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi4(data, size, nrend, o4.data(), jpeg, jpeg_len, status);
+    std::vector<h2j_out_opts5> o5;
+    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi3(const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, uint8_t** jpeg,
                                            size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    std::vector<h2j_out_opts4> o4;
-    for (int r = 0; r < nrend; r++) o4.push_back(opts4_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi4(data, size, nrend, o4.data(), jpeg, jpeg_len, status);
+    std::vector<h2j_out_opts5> o5;
+    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi4(const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (!opts) return -1;
+    std::vector<h2j_out_opts5> o5;
+    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_multi5(const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, uint8_t** jpeg,
                                            size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!jpeg || !jpeg_len || !status || !opts) return -1;

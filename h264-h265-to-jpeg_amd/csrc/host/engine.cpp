@@ -46,6 +46,10 @@
 // bound when this library loads, so a stand-in or an older build selected beside it still loads)
 extern "C" int h2j_gpu_orient(const h2j_gpu_batch*, const h2j_orient*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
+// likewise its finishing stage: K3u and the K4 entry that takes the quantiser scale from the caller
+extern "C" int h2j_gpu_finish(const h2j_gpu_batch*, const h2j_finish*, const int32_t*, const int32_t*, const int32_t*, void*)
+    __attribute__((weak));
+extern "C" int h2j_gpu_jpeg2(const h2j_gpu_batch*, const int32_t*, void*) __attribute__((weak));
 
 namespace h2j {
 namespace {
@@ -181,44 +185,50 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
-// Output options: h2j_out_opts4 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
-// an h2j_out_opts2 item the crop fields, an h2j_out_opts3 item the orientation)
-const h2j_out_opts4 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};  // the JPEG at the decoded size
-std::vector<h2j_out_opts4> opts4_of(int n, const h2j_out_opts* o) {  // o null: all plain
-    std::vector<h2j_out_opts4> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+// Output options: h2j_out_opts5 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
+// an h2j_out_opts2 item the crop fields, an h2j_out_opts3 item the orientation, an h2j_out_opts4 item qscale and
+// sharpen: widen_opts4 in job.h)
+const h2j_out_opts5 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};  // the JPEG at the decoded size
+std::vector<h2j_out_opts5> opts5_of(int n, const h2j_out_opts* o) {  // o null: all plain
+    std::vector<h2j_out_opts5> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
     for (int i = 0; o && i < n; i++) {
         v[i].scale_log2 = o[i].scale_log2;
         v[i].max_dim = o[i].max_dim;
     }
     return v;
 }
-h2j_out_opts4 opts4_of(const h2j_out_opts3& o) {
-    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0,
-                         {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
+h2j_out_opts5 opts5_of(const h2j_out_opts4& o) { return widen_opts4(o); }
+h2j_out_opts5 opts5_of(const h2j_out_opts3& o) {
+    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0,
+                         {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
 }
-h2j_out_opts4 opts4_of(const h2j_out_opts2& o) {
-    return h2j_out_opts4{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0, 0, 0}};
+h2j_out_opts5 opts5_of(const h2j_out_opts2& o) {
+    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
 }
 template <typename T>
-std::vector<h2j_out_opts4> opts4_of(int n, const T* o) {  // h2j_out_opts2 / h2j_out_opts3 items
-    std::vector<h2j_out_opts4> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
-    for (int i = 0; o && i < n; i++) v[i] = opts4_of(o[i]);
+std::vector<h2j_out_opts5> opts5_of(int n, const T* o) {  // h2j_out_opts2 / h2j_out_opts3 items
+    std::vector<h2j_out_opts5> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+    for (int i = 0; o && i < n; i++) v[i] = opts5_of(o[i]);
     return v;
 }
-// the h2j_out_opts4 items of a multi call's h2j_out_opts2 / h2j_out_opts3 items (valid counts)
+// the h2j_out_opts5 items of a multi call's h2j_out_opts2 / h2j_out_opts3 items (valid counts)
 template <typename T>
-std::vector<h2j_out_opts4> multi_opts4(int n, const int32_t* nrend, const T* opts) {
+std::vector<h2j_out_opts5> multi_opts5(int n, const int32_t* nrend, const T* opts) {
     int total = 0;
     for (int i = 0; i < n; i++) total += nrend[i];
-    return opts4_of(total, opts);
+    return opts5_of(total, opts);
 }
-bool reserved_zero(const h2j_out_opts4& o) { return std::all_of(o.reserved, o.reserved + 6, [](int32_t r) { return r == 0; }); }
+bool reserved_zero(const h2j_out_opts5& o) { return std::all_of(o.reserved, o.reserved + 4, [](int32_t r) { return r == 0; }); }
+// finishing (include/h2j.h "Finishing"): a fixed quantiser scale, an unsharp mask
+bool finish_valid(const h2j_out_opts5& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
+bool finishing(const FrameJob::Output& o) { return o.qscale != 0 || o.sharpen != 0; }
 // the orientation (0, 2..8) the options name for a picture whose display orientation SEI says sei_orient
-int resolve_orient(const h2j_out_opts4& o, int sei_orient) {
+int resolve_orient(const h2j_out_opts5& o, int sei_orient) {
     const int r = o.orient == H2J_ORIENT_AUTO ? sei_orient : o.orient;
     return r == 1 ? 0 : r;
 }
 const char kNoStageMessage[] = "the kernel library has no orientation stage (h2j_gpu_orient): oriented output needs a newer libh2j_hip.so";
+const char kNoFinishMessage[] = "the kernel library has no finishing stage (h2j_gpu_finish, h2j_gpu_jpeg2): qscale and sharpen need a newer libh2j_hip.so";
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
 // max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does).
 // Exact-size output (h2j_out_opts2): the size h2j_fit_size gives.
@@ -228,9 +238,9 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
 }
 // what can be said of the options before the picture's size is known (an item none of whose renditions
 // passes is not parsed); the window's place in the picture is checked by resolve_output
-bool out_opts_valid(const h2j_out_opts4& o) {
+bool out_opts_valid(const h2j_out_opts5& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8) return false;
+    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o)) return false;
     if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
     if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
         if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
@@ -239,7 +249,7 @@ bool out_opts_valid(const h2j_out_opts4& o) {
     if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts4& o, int w, int h) {
+int resolve_scale(const h2j_out_opts5& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
@@ -252,8 +262,10 @@ int resolve_scale(const h2j_out_opts4& o, int w, int h) {
 // resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest.
 // Orientation (include/h2j.h "Orientation"; sei_orient: the picture's, for H2J_ORIENT_AUTO) comes first: the
 // rule runs on the oriented size, the window is in the oriented picture
-FrameJob::Output resolve_output(const h2j_out_opts4& o, int W, int H, int sei_orient) {
+FrameJob::Output resolve_output(const h2j_out_opts5& o, int W, int H, int sei_orient) {
     FrameJob::Output out;
+    out.qscale = o.qscale;
+    out.sharpen = o.sharpen;
     out.orient = resolve_orient(o, sei_orient);
     if (out.orient >= 5) std::swap(W, H);
     int64_t x = o.crop_x, y = o.crop_y, w = o.crop_w ? o.crop_w : W - x, h = o.crop_h ? o.crop_h : H - y;
@@ -294,7 +306,7 @@ FrameJob::Output resolve_output(const h2j_out_opts4& o, int W, int H, int sei_or
 }
 // W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
 // message they always got
-std::string out_opts_message(const h2j_out_opts4& o, int W = 0, int H = 0, int sei_orient = 0) {
+std::string out_opts_message(const h2j_out_opts5& o, int W = 0, int H = 0, int sei_orient = 0) {
     std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
@@ -304,6 +316,8 @@ std::string out_opts_message(const h2j_out_opts4& o, int W = 0, int H = 0, int s
         m += "; crop " + std::to_string(o.crop_x) + ", " + std::to_string(o.crop_y) + ", " + std::to_string(o.crop_w) + " x " +
              std::to_string(o.crop_h) + " (even, >= 0, at least 2 x 2 inside the picture; cover needs a box and excludes stretch, scale_log2, max_dim)";
     if (o.orient != 0) m += "; orient " + std::to_string(o.orient) + " (0..8, -1: the stream's display orientation)";
+    if (o.qscale != 0 || o.sharpen != 0)
+        m += "; qscale " + std::to_string(o.qscale) + " (0 or 2..31), sharpen " + std::to_string(o.sharpen) + " (0..64)";
     if (!(window && W > 0 && H > 0)) return m;
     const int ro = (o.orient >= H2J_ORIENT_AUTO && o.orient <= 8) ? resolve_orient(o, sei_orient) : 0;
     if (ro >= 5) std::swap(W, H);
@@ -311,20 +325,23 @@ std::string out_opts_message(const h2j_out_opts4& o, int W = 0, int H = 0, int s
     if (ro) m += " at orientation " + std::to_string(ro);
     return m;
 }
+// the message of an output that failed with H2J_ERR_NO_STAGE: the stage the kernel library lacks
+const char* no_stage_message(const FrameJob::Output& o) { return (o.orient && !h2j_gpu_orient) ? kNoStageMessage : kNoFinishMessage; }
 // the outputs of a parsed job: every rendition's is resolved on its own, and invalid options fail that
 // rendition alone
-void resolve_outputs(const h2j_out_opts4* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts5* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
         if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h, job.sei_orient);
         else job.outs[r].error = H2J_ERR_OUT_OPTS;
         if (job.outs[r].error == 0 && job.outs[r].orient && !h2j_gpu_orient) job.outs[r].error = H2J_ERR_NO_STAGE;
+        if (job.outs[r].error == 0 && finishing(job.outs[r]) && !(h2j_gpu_finish && h2j_gpu_jpeg2)) job.outs[r].error = H2J_ERR_NO_STAGE;
     }
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts4* o, int nr, FrameJob& job, bool* ran) {
+int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts5* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -421,7 +438,7 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts4> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    std::vector<h2j_out_opts5> opts;           // output options per rendition, item-major (a plain item has one rendition)
     std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
     int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
@@ -572,7 +589,9 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
         put(p.at.scale, p.scalemap.data(), p.scalemap.size() * sizeof(h2j_scaled));
         put(p.at.pyr, p.pyrmap.data(), p.pyrmap.size() * sizeof(h2j_pyramid));
         put(p.at.orient, p.orientmap.data(), p.orientmap.size() * sizeof(h2j_orient));
+        put(p.at.finish, p.finmap.data(), p.finmap.size() * sizeof(h2j_finish));
     }
+    if (p.qforced) put(p.at.qforce, p.vqscale.data(), static_cast<size_t>(p.nv) * 4);
     const std::vector<FrameJob>& jobs = *s.jobs;
     auto pack = [&](int k) {  // the frame's record ranges are where plan_chunk numbered them
         const FrameJob& j = jobs[s.live[k]];
@@ -660,8 +679,17 @@ int Engine::launch(Slot& s, const Slot* after) {
                                            p.orient_first, p.orient_count, p.orient_tiles, st)))
         return drain_fail(s, h2j_gpu_orient ? h2j_gpu_last_error() : kNoStageMessage);
     if (s.stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
+    // K3u: only in chunks with sharpened outputs (they exist only when the kernel library has the stage)
+    if (s.stages >= 3 && !p.finmap.empty() &&
+        (!h2j_gpu_finish || h2j_gpu_finish(&b, reinterpret_cast<const h2j_finish*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.finish),
+                                           p.fin_first, p.fin_count, p.fin_tiles, st)))
+        return drain_fail(s, h2j_gpu_finish ? h2j_gpu_last_error() : kNoFinishMessage);
     h2j_gpu_event_record(s.ev[EV_SCALE], st);
-    if (s.stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    // K4: through h2j_gpu_jpeg2 only in chunks with a forced quantiser scale (likewise)
+    if (s.stages >= 4 && p.qforced) {
+        if (!h2j_gpu_jpeg2 || h2j_gpu_jpeg2(&jb, reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.qforce), st))
+            return drain_fail(s, h2j_gpu_jpeg2 ? h2j_gpu_last_error() : kNoFinishMessage);
+    } else if (s.stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K4], st);
     if (s.entropy && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K5], st);
@@ -853,6 +881,13 @@ static double hbm_estimate(const FrameJob& j) {
             oriented |= 1 << j.outs[r].orient;
             est += 1.5 * j.hdr.out_w * j.hdr.out_h * (j.hdr.bit_depth > 8 ? 2.0 : 1.0) + 4096;
         }
+    // sharpened outputs: the 8-bit planes K3u writes (1.5 B per output sample)
+    for (int r = 0; r < j.nouts; r++) {
+        const FrameJob::Output& o = j.outs[r];
+        if (o.error || !o.sharpen) continue;
+        est += 1.5 * (o.scale_log2 == H2J_SCALE_RESAMPLE ? static_cast<double>(o.fit_w) * o.fit_h
+                                                           : static_cast<double>(o.win_w) * o.win_h / (1 << 2 * o.scale_log2)) + 4096;
+    }
     return est;
 }
 // JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
@@ -943,7 +978,7 @@ void Engine::drive_loop() {
                     if (b->status[o] == 0) continue;
                     if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
                     else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h, (*jobs)[i].sei_orient);
-                    else if (b->status[o] == H2J_ERR_NO_STAGE) b->msg[o] = kNoStageMessage;
+                    else if (b->status[o] == H2J_ERR_NO_STAGE) b->msg[o] = no_stage_message((*jobs)[i].outs[o - b->rbase[i]]);
                 }
             }
         if (b->jobset >= 0) jobset_busy[b->jobset] = false;
@@ -1161,7 +1196,7 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            const h2j_out_opts5* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                             int* status, bool latency) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
@@ -1213,14 +1248,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::opts4_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::opts5_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts4_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts5_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1253,7 +1288,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts4_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts5_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1261,7 +1296,7 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts4_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts5_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1278,7 +1313,7 @@ int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1286,11 +1321,11 @@ int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* dat
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
-int64_t h2j_engine_submit_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                                 const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+int64_t h2j_engine_submit_multi5(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                 const h2j_out_opts5* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
@@ -1302,7 +1337,7 @@ int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data,
                                int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1311,12 +1346,12 @@ int h2j_engine_transcode_multi3(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts4(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
-int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                                const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+int h2j_engine_transcode_multi5(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts5* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
@@ -1324,11 +1359,34 @@ int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data
     return h2j_engine_wait(w, t);
 }
 
+int64_t h2j_engine_submit_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                 const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                 int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+}
+
+int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts4* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                int* status) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    return h2j_engine_wait(w, t);
+}
+
+int h2j_crop_window4(int w, int h, const h2j_out_opts4* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
+    if (!o) return H2J_ERR_OUT_OPTS;
+    const h2j_out_opts5 o5 = h2j::opts5_of(*o);
+    return h2j_crop_window5(w, h, &o5, sei_orient, win, ow, oh, orient);
+}
+
 int h2j_crop_window(int w, int h, const h2j_out_opts3* o, int32_t* win, int* ow, int* oh) {
     if (!o) return H2J_ERR_OUT_OPTS;
-    const h2j_out_opts4 o4 = h2j::opts4_of(*o);
+    const h2j_out_opts5 o5 = h2j::opts5_of(*o);
     int orient = 0;
-    return h2j_crop_window4(w, h, &o4, 0, win, ow, oh, &orient);
+    return h2j_crop_window5(w, h, &o5, 0, win, ow, oh, &orient);
 }
 
 int h2j_stream_orientation(const uint8_t* data, size_t size) {
@@ -1338,7 +1396,7 @@ int h2j_stream_orientation(const uint8_t* data, size_t size) {
     return h2j::stream_display_orientation(data, size, codec);
 }
 
-int h2j_crop_window4(int w, int h, const h2j_out_opts4* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
+int h2j_crop_window5(int w, int h, const h2j_out_opts5* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
     if (!o || !win || !ow || !oh || !orient || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
         sei_orient > 8 || !h2j::out_opts_valid(*o))
         return H2J_ERR_OUT_OPTS;
@@ -1377,7 +1435,7 @@ int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts4* o = &h2j::kPlainOutput, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts5* o = &h2j::kPlainOutput, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -1484,8 +1542,8 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
-// (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts4* o, int nrend, int pick,
+// (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too; 12: qscale and sharpen too)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts5* o, int nrend, int pick,
                               uint8_t* planes_out, size_t cap, int* info, int info_n = 4) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
@@ -1497,14 +1555,15 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
     if (single_job(w, data, size, o, nrend)) return -2;
     for (int r = 0; r < nrend; r++)
         if (e.jobs[0].outs[r].error == H2J_ERR_NO_STAGE) {
-            e.fail(h2j::kNoStageMessage);
+            e.fail(h2j::no_stage_message(e.jobs[0].outs[r]));
             return H2J_ERR_NO_STAGE;
         } else if (e.jobs[0].outs[r].error) {  // a window outside the picture
             e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h, e.jobs[0].sei_orient));
             return H2J_ERR_OUT_OPTS;
         }
     Slot& s = e.slot[0];
-    if (e.enqueue(s, 3, false) || e.sync(s)) return -3;
+    // (12 entries: K4 runs too, for the quantiser scale it used)
+    if (e.enqueue(s, info_n >= 12 ? 4 : 3, false) || e.sync(s)) return -3;
     // the picture K4 would read: the JPEG source view of the rendition
     const h2j_frame& f = s.plan.frames[0];
     const int vi = s.plan.rends[static_cast<size_t>(pick)].view;
@@ -1530,12 +1589,19 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
         info[8] = wo.orient;
         info[9] = e.jobs[0].sei_orient;
     }
+    if (info_n >= 12) {
+        h2j_jstat st;
+        if (h2j_gpu_memcpy_d2h(&st, static_cast<uint8_t*>(s.d_arena.p) + v.jstat, sizeof(st), s.stream) || h2j_gpu_stream_sync(s.stream))
+            return e.fail(h2j_gpu_last_error());
+        info[10] = st.qscale;
+        info[11] = wo.sharpen;
+    }
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
     size_t bytes = 0;  // the view's planes in the arena, from v.pic2
     for (int c = 0; c < 3; c++) {
         // (an unscaled oriented view lies in the oriented planes, whose rows end with the oriented picture's)
-        const int rows = sc.scale_log2 ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
+        const int rows = (sc.scale_log2 || wo.sharpen) ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
         bytes = std::max(bytes, (static_cast<size_t>(v.pic_off[c]) + static_cast<size_t>(v.pic_stride[c]) * rows) * pel);
     }
     std::vector<uint8_t> tmp(bytes);
@@ -1559,13 +1625,13 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts4 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};
+    const h2j_out_opts5 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts4 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, {0, 0, 0, 0, 0, 0}};
+    const h2j_out_opts5 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
@@ -1573,21 +1639,28 @@ int h2j_engine_decode_multi(h2j_engine* w, const uint8_t* data, size_t size, int
                             uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts4_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
+    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
 }
 
 int h2j_engine_decode_multi3(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts4_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 8);
+    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 8);
+}
+
+int h2j_engine_decode_multi5(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, int pick,
+                             uint8_t* planes_out, size_t cap, int* info) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (pick < 0 || pick >= nrend) return -1;
+    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, 12);
 }
 
 int h2j_engine_decode_multi4(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (pick < 0 || pick >= nrend) return -1;
-    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, 10);
+    if (pick < 0 || pick >= nrend || !opts) return -1;
+    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 10);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

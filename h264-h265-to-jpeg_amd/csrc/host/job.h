@@ -45,6 +45,9 @@ struct FrameJob {
         // the orientation of the picture the window lies in: 0 as decoded, 2..8 (include/h2j.h); the window
         // is then in the coordinates of the oriented picture.  0: the job is the one without an orientation
         int orient = 0;
+        // finishing (include/h2j.h "Finishing"): the quantiser scale K4 is to use (0: the rate control's) and the
+        // strength of the unsharp mask K3u applies to the output's 8-bit luma (0: none)
+        int qscale = 0, sharpen = 0;
     };
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;
@@ -65,6 +68,14 @@ struct FrameJob {
         nouts = 0;
     }
 };
+
+// h2j_out_opts5 is the engine's one option type.  An h2j_out_opts4 item is the h2j_out_opts5 item with qscale and
+// sharpen 0; the two words they took over were reserved there and still must be 0: a non-zero one stays a
+// non-zero reserved word
+inline h2j_out_opts5 widen_opts4(const h2j_out_opts4& o) {
+    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient, 0, 0,
+                         {o.reserved[0] | o.reserved[1] | o.reserved[2], o.reserved[3], o.reserved[4], o.reserved[5]}};
+}
 
 // Offsets of the scaling-factor tables inside FrameJob::sl
 enum { H2J_SL_S0 = 0, H2J_SL_S1 = 48, H2J_SL_S2 = 240, H2J_SL_S3 = 1008, H2J_SL_BYTES = 2032 };

@@ -46,6 +46,16 @@ class OutOpts4(ctypes.Structure):
                 ("orient", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
 
 
+class OutOpts5(ctypes.Structure):
+    """include/h2j.h h2j_out_opts5: h2j_out_opts4 and the finishing options (a fixed JPEG quantiser scale, an
+    unsharp mask on the GPU)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("orient", ctypes.c_int32), ("qscale", ctypes.c_int32), ("sharpen", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
 FIT_COVER = 2  # include/h2j.h H2J_FIT_COVER
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
@@ -178,6 +188,24 @@ def load_library() -> ctypes.CDLL:
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         lib.h2j_stream_orientation.restype = ctypes.c_int
         lib.h2j_stream_orientation.argtypes = [u8p, ctypes.c_size_t]
+    # finishing (qscale, sharpen): likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_multi5"):
+        opt5p = ctypes.POINTER(OutOpts5)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi5.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi5.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt5p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_engine_submit_multi5.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi5.argtypes = lib.h2j_engine_transcode_multi5.argtypes
+        lib.h2j_engine_decode_multi5.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi5.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt5p, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi5.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi5.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt5p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_crop_window5.restype = ctypes.c_int
+        lib.h2j_crop_window5.argtypes = [ctypes.c_int, ctypes.c_int, opt5p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -265,7 +293,16 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen")
+
+
+def _finish_value(v, what, name):
+    """qscale / sharpen as h2j_out_opts5 takes them: an int (the engine checks the range); None is 0."""
+    if v is None:
+        return 0
+    if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+        return int(v)
+    raise ValueError(f"{what}: {name} {v!r} is not an int")
 
 
 def _orient_value(v, what):
@@ -286,14 +323,17 @@ def _is_window(v):
 def rendition_spec(spec):
     """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2; with
     a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3; with an orient
-    key those and orient: the fields of h2j_out_opts4.
+    key those and orient: the fields of h2j_out_opts4; with a qscale or sharpen key those (orient 0 if the spec
+    names none), qscale and sharpen: the fields of h2j_out_opts5.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
     of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
     to the edge) and cover (a (w, h) box: the largest centred part of the window with the box's aspect, at
     the box's size) and orient (0..8, the EXIF orientation that makes the picture upright, or "auto": the one
     the stream's display orientation SEI names; crop, cover, scale and fit then act on the oriented
-    picture).  Values are not range-checked here: the engine fails a rendition
+    picture), qscale (2..31: the JPEG quantiser scale instead of the rate control's; 0: the rate control's) and
+    sharpen (1..64: an unsharp mask of strength sharpen / 16 on the luma of the rendition's final 8-bit planes;
+    0: none).  Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
         raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
@@ -304,7 +344,12 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen)")
+        if "qscale" in spec or "sharpen" in spec:  # the h2j_out_opts5 fields, whatever else the spec names
+            rest = dict(spec)
+            q = _finish_value(rest.pop("qscale", None), f"rendition {spec!r}", "qscale")
+            a = _finish_value(rest.pop("sharpen", None), f"rendition {spec!r}", "sharpen")
+            return (tuple(rendition_spec(rest)) + (0,) * 5)[:10] + (q, a)
         fit = spec.get("fit")
         if fit is not None and not _is_pair(fit):
             raise ValueError(f"rendition {spec!r}: fit is not a (w, h) pair")
@@ -382,7 +427,9 @@ def _multi_opts(per_item):
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    if any(len(t) > 9 for t in flat):  # an orientation: the multi4 calls
+    if any(len(t) > 10 for t in flat):  # a finishing option: the multi5 calls
+        opts = (OutOpts5 * len(flat))(*[OutOpts5(*(tuple(t) + (0,) * 7)[:12]) for t in flat])
+    elif any(len(t) > 9 for t in flat):  # an orientation: the multi4 calls
         opts = (OutOpts4 * len(flat))(*[OutOpts4(*(tuple(t) + (0,) * 5)[:10]) for t in flat])
     elif any(len(t) > 5 for t in flat):
         opts = (OutOpts3 * len(flat))(*[OutOpts3(*(tuple(t) + (0, 0, 0, 0))[:9]) for t in flat])
@@ -418,8 +465,20 @@ def _per_item_orient(orient, n):
     return [None if x is None else _orient_value(x, "orient") for x in v]
 
 
-def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None):
-    """Per-item rendition dicts of transcode()'s keywords when crop, cover or orient is given."""
+def _per_item_finish(v, n, name):
+    """qscale / sharpen (None, one int for every item, or a per-item sequence of ints or None) -> n values or None."""
+    if v is None:
+        return [None] * n
+    if isinstance(v, (int, np.integer)):
+        return [_finish_value(v, name, name)] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"{name}: {len(v)} entries for {n} streams")
+    return [None if x is None else _finish_value(x, name, name) for x in v]
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None):
+    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale or sharpen is given."""
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
     ft = [None] * n if fit is None else _per_item_fit(fit, n)
     if isinstance(stretch, (bool, np.bool_)) or stretch is None:
@@ -431,6 +490,7 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None):
     cr = _per_item_shape(crop, n, "crop", _is_window, "an (x, y, w, h) window")
     cv = _per_item_shape(cover, n, "cover", _is_pair, "a (w, h) pair")
     orr = _per_item_orient(orient, n)
+    qs, sh = _per_item_finish(qscale, n, "qscale"), _per_item_finish(sharpen, n, "sharpen")
     out = []
     for i in range(n):
         d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
@@ -442,6 +502,10 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None):
             d["cover"] = cv[i]
         if orr[i] is not None:
             d["orient"] = orr[i]
+        if qs[i] is not None:
+            d["qscale"] = qs[i]
+        if sh[i] is not None:
+            d["sharpen"] = sh[i]
         out.append([d])
     return out
 
@@ -539,7 +603,7 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False, crop=None, cover=None, orient=None) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -559,12 +623,16 @@ class Engine:
 
         orient: the JPEG of the picture rotated / mirrored on the GPU (h2j_out_opts4): 0..8 (the EXIF
         orientation that makes the picture upright) or "auto" (the stream's display orientation SEI), for every
-        item or a per-item sequence of values or None; every other option acts on the oriented picture."""
+        item or a per-item sequence of values or None; every other option acts on the oriented picture.
+
+        qscale (2..31: that JPEG quantiser scale instead of the rate control's) and sharpen (1..64: an unsharp
+        mask of strength sharpen / 16 on the output's luma, on the GPU) (h2j_out_opts5): an int for every item
+        or a per-item sequence of ints or None."""
         n = len(streams)
         if n == 0:
             return []
-        if crop is not None or cover is not None or orient is not None:  # one rendition per item through the multi3 / multi4 call
-            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient))
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen)):  # one rendition per item through the multi3 / multi4 / multi5 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen))
             self.last_status = [st[0] for st in self.last_status]
             return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
@@ -614,7 +682,7 @@ class Engine:
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            call = {OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
+            call = {OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
             call = getattr(self._lib, call)
             rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if not any(status[i] == -50 for i in range(total)):
@@ -655,7 +723,7 @@ class Engine:
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
             held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item))
-            call = {OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
+            call = {OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
             call = getattr(self._lib, call)
             t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
             if t <= 0:
@@ -675,8 +743,11 @@ class Engine:
         """(Y, U, V uint8 numpy, (W_o, H_o), mode): the 8-bit planes the JPEG stage reads for rendition
         `pick` of this picture with all of `renditions` (a list of specs) in flight; mode 0 unscaled,
         1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi).
-        Renditions with a crop or cover key go through decode_multi3, with an orient key through decode_multi4."""
+        Renditions with a crop or cover key go through decode_multi3, with an orient key through decode_multi4,
+        with a qscale or sharpen key through decode_multi5."""
         specs = normalize_renditions([list(renditions)], 1)[0]
+        if any(len(t) > 10 for t in specs):
+            return self.decode_multi5(stream, renditions, pick)[:5]
         if any(len(t) > 9 for t in specs):
             return self.decode_multi4(stream, renditions, pick)[:5]
         if any(len(t) > 5 for t in specs):
@@ -731,6 +802,25 @@ class Engine:
         return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
                 int(info[8]), int(info[9]))
 
+    def decode_multi5(self, stream: bytes, renditions, pick: int):
+        """decode_multi through h2j_engine_decode_multi5 (finishing): decode_multi4's result, then the quantiser
+        scale K4 used for the rendition (the forced one, or the rate control's) and its sharpen.  The planes are
+        what K4 reads: those of a sharpened rendition are the sharpened planes K3u wrote."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        total = len(specs)
+        opts = (OutOpts5 * total)(*[OutOpts5(*(tuple(t) + (0,) * 7)[:12]) for t in specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 12)()
+        rc = self._lib.h2j_engine_decode_multi5(self._h, buf, len(stream), total, opts, int(pick),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi5 failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
+                int(info[8]), int(info[9]), int(info[10]), int(info[11]))
+
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
         return self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
@@ -753,17 +843,20 @@ class Engine:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
     def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
-                        stretch=False, crop=None, cover=None, orient=None) -> List[List[Optional[bytes]]]:
+                        stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
         (each a scalar or a per-item sequence).  fit / stretch likewise: one (w, h) pair / bool for
         every picture, or one entry per batch (each what transcode() takes).  crop / cover likewise: one
         window / box for every picture, or one entry per batch; orient likewise: one value (0..8 or "auto")
-        for every picture, or one entry per batch."""
-        if crop is not None or cover is not None or orient is not None:
+        for every picture, or one entry per batch; qscale and sharpen likewise: one int for every picture, or one
+        entry per batch."""
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen)):
             one_orient = isinstance(orient, (str, int, np.integer))
-            for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover)), ("orient", orient, one_orient)):
+            one_int = lambda v: isinstance(v, (int, np.integer))
+            for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover)), ("orient", orient, one_orient),
+                                 ("qscale", qscale, one_int(qscale)), ("sharpen", sharpen, one_int(sharpen))):
                 if v is not None and not one and len(v) != len(batches):
                     raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
             pick = lambda v, one, bi: v if v is None or one else v[bi]
@@ -772,7 +865,8 @@ class Engine:
                                    pick(max_dim, isinstance(max_dim, (int, np.integer)), bi),
                                    pick(fit, _is_pair(fit), bi), pick(stretch, isinstance(stretch, (bool, np.bool_)), bi),
                                    pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi),
-                                   pick(orient, one_orient, bi))
+                                   pick(orient, one_orient, bi), pick(qscale, one_int(qscale), bi),
+                                   pick(sharpen, one_int(sharpen), bi))
                      for bi, streams in enumerate(batches)]
             res = self._multi_async(batches, rends)
             self.last_status = [[st[0] for st in b] for b in self.last_status]

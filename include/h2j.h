@@ -232,6 +232,47 @@ int64_t h2j_engine_submit_multi4(h2j_engine *e, int n, const uint8_t *const *dat
                                  const int32_t *nrend, const h2j_out_opts4 *opts, uint8_t *out, size_t out_cap,
                                  size_t *out_off, size_t *out_len, int *status);
 
+/* Finishing: a fixed JPEG quantiser scale and an unsharp mask, per rendition (DESIGN.md "Finishing (K3u,
+ * forced qscale)").  h2j_out_opts5 is h2j_out_opts4 with two of its reserved words named.
+ * qscale: 0: the rate control's quantiser scale, as every other call.  2..31 (the range the rate control clips
+ *   to): that scale -- the quantisation matrix and the quantiser (A.5) of it, the rate control
+ *   formula skipped.  The scale equal to the one the rate control picks returns the bytes of the call without it.
+ * sharpen: 0: off.  1..64: an unsharp mask of strength sharpen / 16 on the LUMA of the rendition's final 8-bit
+ *   planes -- after orientation, window and scale / fit: the planes h2j_engine_decode_multi4 shows.  For the
+ *   8-bit luma plane P (H x W, the JPEG size), coordinates clamped to the plane:
+ *     S(x, y) = sum of w[dy][dx] P(x + dx, y + dy), dy, dx in -1..1, w = [1 2 1; 2 4 2; 1 2 1]
+ *     D = 16 P - S          out = clip(P + ((sharpen D + 128) >> 8), 0, 255)       (arithmetic shift)
+ *   integer arithmetic with one rounding, inside int32.  The chroma is the unsharpened 8-bit chroma.
+ * The sharpened planes are the picture: the rendition's bytes are exactly those the same call without sharpen
+ * returns for a picture whose 8-bit planes are the sharpened planes -- the rate control runs on the sharpened
+ * luma when qscale is 0.  Every call without the two options returns the bytes it returned.
+ * qscale outside {0, 2..31}, sharpen outside 0..64 or non-zero reserved: that rendition fails alone with
+ * H2J_ERR_OUT_OPTS.  On a kernel library without the stage (h2j_gpu_finish, h2j_gpu_jpeg2) a rendition that names
+ * either option fails alone with H2J_ERR_NO_STAGE. */
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts4 */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window of the oriented picture */
+    int32_t orient;                                   /* 0..8, or H2J_ORIENT_AUTO */
+    int32_t qscale;                                   /* 0, or 2..31 */
+    int32_t sharpen;                                  /* 0..64, in 1/16 */
+    int32_t reserved[4];                              /* must be 0 */
+} h2j_out_opts5;                                      /* 64 bytes */
+
+/* h2j_crop_window4 with h2j_out_opts5: the same window, size and orientation, and the two range checks.
+ * Returns 0, or H2J_ERR_OUT_OPTS (nothing is written). */
+int h2j_crop_window5(int w, int h, const h2j_out_opts5 *o, int sei_orient, int32_t *win, int *ow, int *oh, int *orient);
+
+/* h2j_engine_transcode_multi4 / h2j_engine_submit_multi4 with h2j_out_opts5; an h2j_out_opts4 item is the
+ * h2j_out_opts5 item with qscale and sharpen 0 (the multi4 calls keep rejecting non-zero reserved words).
+ * Renditions of one item that resolve to the same (orientation, window, output, qscale, sharpen) are encoded
+ * once; renditions that differ only in qscale or sharpen each run the scale stage for themselves. */
+int h2j_engine_transcode_multi5(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts5 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status);
+int64_t h2j_engine_submit_multi5(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                 const int32_t *nrend, const h2j_out_opts5 *opts, uint8_t *out, size_t out_cap,
+                                 size_t *out_off, size_t *out_len, int *status);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -271,13 +312,18 @@ int h2j_engine_decode_multi3(h2j_engine *e, const uint8_t *data, size_t size, in
  * At mode 0 the planes of an oriented rendition are the oriented planes K3o wrote, through K4's 8-bit conversion. */
 int h2j_engine_decode_multi4(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts4 *opts,
                              int pick, uint8_t *planes_out, size_t cap, int *info);
+/* The same with h2j_out_opts5; info has 12 entries: [0..9] as above, [10] = the quantiser scale K4 used for the
+ * rendition (the forced one, or the rate control's), [11] = its sharpen.  The planes are what K4 reads: those of a
+ * sharpened rendition are the sharpened planes K3u wrote. */
+int h2j_engine_decode_multi5(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts5 *opts,
+                             int pick, uint8_t *planes_out, size_t cap, int *info);
 /* Timing of the batch the last h2j_engine_transcode / h2j_engine_wait returned, milliseconds:
  * [0] parse (host, wall, from submission)  [1] h2d  [2] recon  [3] deblock  [4] sao
  * [5] jpeg (GPU)  [6] d2h  [7] huffman (host, wall)  [8] total (wall)
  * [9] frames  [10] algorithmic bytes of the GPU pixel path  [11] GPU entropy
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
- * h2j.py  [22] K3o / K3s / K3r / K3p orientation, scaled- and exact-size-output stage (GPU)  [23] renditions: JPEG outputs
+ * h2j.py  [22] K3o / K3s / K3r / K3p / K3u orientation, scaled- and exact-size-output and finishing stage (GPU)  [23] renditions: JPEG outputs
  * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran. */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
@@ -316,6 +362,9 @@ int h2j_h265_to_jpeg_mem_multi3(const uint8_t *data, size_t size, int nrend, con
                                 size_t *jpeg_len, int *status);
 /* the same with h2j_out_opts4 (orientation): concurrent callers with different orientations still share GPU batches */
 int h2j_h265_to_jpeg_mem_multi4(const uint8_t *data, size_t size, int nrend, const h2j_out_opts4 *opts, uint8_t **jpeg,
+                                size_t *jpeg_len, int *status);
+/* the same with h2j_out_opts5 (finishing): concurrent callers with different finishing options still share GPU batches */
+int h2j_h265_to_jpeg_mem_multi5(const uint8_t *data, size_t size, int nrend, const h2j_out_opts5 *opts, uint8_t **jpeg,
                                 size_t *jpeg_len, int *status);
 void h2j_free(void *p);
 

@@ -98,6 +98,13 @@ constexpr int h2j_k3o_plane_tiles(int ow, int oh, int pel, bool transposing) {
 constexpr int h2j_k3o_tiles(int ow, int oh, int pel, bool transposing) {
     return h2j_k3o_plane_tiles(ow, oh, pel, transposing) + 2 * h2j_k3o_plane_tiles(ow / 2, oh / 2, pel, transposing);
 }
+/* K3u (finishing) workgroups (256 lanes: 64 dwords of 4 output samples x 4 lane rows of H2J_K3U_ROWS output
+ * rows each) of one plane and of a picture */
+#define H2J_K3U_ROWS 4
+constexpr int h2j_k3u_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * ((h + 4 * H2J_K3U_ROWS - 1) / (4 * H2J_K3U_ROWS)); }
+constexpr int h2j_k3u_tiles(int jpeg_w, int jpeg_h) {
+    return h2j_k3u_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3u_plane_tiles(jpeg_w / 2, jpeg_h / 2);
+}
 /* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
  * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
@@ -215,10 +222,25 @@ int h2j_gpu_scale(const h2j_gpu_batch *b, void *stream);
 #define H2J_ORIENT_CLASSES 4
 int h2j_gpu_orient(const h2j_gpu_batch *b, const h2j_orient *map, const int32_t *first, const int32_t *count,
                    const int32_t *tiles, void *stream);
+/* K3u: the sharpened outputs (h2j_finish, a device array), grouped by source class (0: the 8-bit planes K3s /
+ * K3r / K3p wrote, h2j_finish.wide; 1: another 8-bit source; 2: a 16-bit source): source planes -> the 8-bit
+ * planes at h2j_finish.dst, the luma through the 3 x 3 unsharp mask (DESIGN.md "Finishing (K3u, forced
+ * qscale)"), the chroma copied through K4's 8-bit conversion.  first / count / tiles: per class (host arrays of
+ * H2J_FINISH_CLASSES), tiles the most workgroups one output of the class needs (h2j_k3u_tiles); one launch per
+ * class present.  Runs after h2j_gpu_scale, whose outputs it reads, and before K4.  A kernel library older
+ * than the stage lacks the symbol (and h2j_gpu_jpeg2): the host library resolves both when it loads and fails
+ * finishing renditions alone (H2J_ERR_NO_STAGE) */
+#define H2J_FINISH_CLASSES 3
+int h2j_gpu_finish(const h2j_gpu_batch *b, const h2j_finish *map, const int32_t *first, const int32_t *count,
+                   const int32_t *tiles, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat
  * (variance, rate control, FDCT + quantiser + zigzag, symbol histograms) */
 int h2j_gpu_jpeg(const h2j_gpu_batch *b, void *stream);
+/* h2j_gpu_jpeg with the quantiser scale of some views set by the caller: qforce is a device array of one int32
+ * per view of b (b->nframes entries), 0: the rate control's scale, 2..31: that scale -- K4b skips the rate
+ * control formula for the view and jstat.qscale holds the value (jstat.lambda: 118 x it).  NULL: h2j_gpu_jpeg */
+int h2j_gpu_jpeg2(const h2j_gpu_batch *b, const int32_t *qforce, void *stream);
 /* K4d alone: Huffman symbol histograms of frame.jcoef -> jstat.hist */
 int h2j_gpu_histogram(const h2j_gpu_batch *b, void *stream);
 /* K5: optimal Huffman tables (jstat.bits/val/code/len) and the entropy-coded

@@ -168,6 +168,28 @@ typedef struct {
     int32_t off[3];                 /* element offset of each oriented plane inside opic (64-byte aligned) */
 } h2j_orient;
 
+/* One sharpened output of a batch (DESIGN.md "Finishing (K3u, forced qscale)"): K3u reads the 8-bit-converted
+ * planes the output's JPEG source view would otherwise be -- the planes K3s / K3r / K3p wrote (8-bit, 16-byte
+ * row groups), or an unscaled frame, window or oriented source in the frame's sample type -- and writes 8-bit
+ * planes of its own at dst: the luma through the unsharp mask, the chroma copied.  The record describes its
+ * source itself (no h2j_frame is read); K4 / K5 read dst through the output's view (pic == pic2 == dst). */
+typedef struct {
+    int32_t w, h;                   /* luma size of the output (the JPEG size; both even) */
+    int32_t sharpen;                /* 1..64: strength in 1/16 */
+    int32_t bit_depth, bit_depth_c; /* of the source samples (8: uint8_t planes, above: uint16_t) */
+    int32_t crop_x, crop_y;         /* the source's first luma sample inside its planes */
+    int32_t wide;                   /* 1: an 8-bit source with 16-byte row groups and no crop (the planes K3s /
+                                       K3r / K3p wrote): aligned dword loads */
+    uint64_t src;                   /* source planes (arena offset, bytes) */
+    int32_t src_stride[3];          /* elements per row */
+    int32_t src_off[3];             /* element offset of each plane inside src */
+    uint64_t dst;                   /* sharpened planes (arena offset, bytes; 256-byte aligned) */
+    int32_t dst_stride[3];          /* bytes per row (h2j_spic_stride: multiples of 16) */
+    int32_t dst_off[3];             /* byte offset of each plane inside dst */
+    uint64_t jstat;                 /* the h2j_jstat of this output: K3u clears its var_sum, K4a sums the sharpened
+                                       picture's */
+} h2j_finish;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;
