@@ -85,7 +85,8 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             const int src = source_of(o);
             for (size_t v = v0; v < p.scaled.size(); v++) {
                 const h2j_scaled& sv = p.scaled[v];
-                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && p.vqscale[v] == o.qscale && p.vsharpen[v] == o.sharpen &&
+                // (a raw output reads any view with its planes: the quantiser scale does not change them)
+                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && (p.vqscale[v] == o.qscale || o.format) && p.vsharpen[v] == o.sharpen &&
                     (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
                     return static_cast<int>(v);
             }
@@ -100,7 +101,19 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             p.vqscale.push_back(o.qscale);
             p.vsharpen.push_back(o.sharpen);
             p.qforced = p.qforced || o.qscale != 0;
+            p.vjpeg.push_back(0);
             return static_cast<int>(p.scaled.size()) - 1;
+        };
+        auto rgb_of = [&](int v, int layout) {  // the raw output of view v in this layout, added if new
+            for (size_t i = 0; i < p.rgbs.size(); i++)
+                if (p.rgbview[i] == v && p.rgbs[i].layout == layout) return static_cast<int>(i);
+            h2j_rgb rec{};
+            rec.w = p.scaled[v].jpeg_w;
+            rec.h = p.scaled[v].jpeg_h;
+            rec.layout = layout;
+            p.rgbs.push_back(rec);
+            p.rgbview.push_back(v);
+            return static_cast<int>(p.rgbs.size()) - 1;
         };
         for (int r = 0; r < j.nouts; r++)
             if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed && !j.outs[r].orient && !j.outs[r].qscale &&
@@ -108,8 +121,19 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
                 view_of(j.outs[r]);
                 break;
             }
-        for (int r = 0; r < j.nouts; r++)
-            if (j.outs[r].error == 0) p.rends.push_back(ChunkPlan::Rend{j.out_base + r, view_of(j.outs[r])});
+        // with raw outputs among them the JPEG renditions name their views first, in their order, so that a raw
+        // output finds the view of a JPEG rendition with its planes wherever the two stand in the list
+        bool raw = false;
+        for (int r = 0; r < j.nouts; r++) raw = raw || (j.outs[r].error == 0 && j.outs[r].format);
+        for (int r = 0; raw && r < j.nouts; r++)
+            if (j.outs[r].error == 0 && !j.outs[r].format) view_of(j.outs[r]);
+        for (int r = 0; r < j.nouts; r++) {
+            const FrameJob::Output& o = j.outs[r];
+            if (o.error != 0) continue;
+            const int v = view_of(o);
+            if (!o.format) p.vjpeg[v] = 1;
+            p.rends.push_back(ChunkPlan::Rend{j.out_base + r, v, o.format ? rgb_of(v, o.format) : -1});
+        }
         d.max_w = std::max(d.max_w, f.width);
         d.max_h = std::max(d.max_h, f.height);
         if (f.codec == H2J_CODEC_HEVC) d.max_ctbs = std::max(d.max_ctbs, f.ctb_w * f.ctb_h);
@@ -120,8 +144,9 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     for (const h2j_scaled& sc : p.scaled) {
         d.max_mcu = std::max(d.max_mcu, static_cast<int>(view_blocks(sc) / 6));
         nblk += view_blocks(sc);
-        p.px += static_cast<double>(sc.jpeg_w) * sc.jpeg_h;
     }
+    for (int v = 0; v < p.nv; v++)  // the payload estimate: the views that get a JPEG
+        if (p.vjpeg[v]) p.px += static_cast<double>(p.scaled[v].jpeg_w) * p.scaled[v].jpeg_h;
     p.tiles = (d.max_mcu * 6 + 255) / 256;
     p.seg_cap = nblk * kSegBytesPerBlock + 16 * static_cast<size_t>(p.nv);
     // the records' places in the staging buffer
@@ -135,7 +160,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     p.at.bytes = c.off;  // the maps follow (layout_maps)
 }
 
-// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][jcoef][res][aux]
+// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][rgb][jcoef][res][aux]
 void layout_arena(ChunkPlan& p) {
     Cursor a;
     for (h2j_frame& f : p.frames) {
@@ -215,6 +240,9 @@ void layout_arena(ChunkPlan& p) {
         p.vfin[v] = static_cast<int>(p.fins.size());
         p.fins.push_back(rec);
     }
+    p.rgb_base = a.off;  // the RGB pixels K3c writes (raw outputs only): one region, each output 256-byte aligned
+    for (h2j_rgb& rec : p.rgbs) rec.dst_off = a.take(3 * static_cast<size_t>(rec.w) * rec.h);
+    p.rgb_bytes = a.off - p.rgb_base;
     for (int v = 0; v < p.nv; v++) {  // per view: dense int16 plane (inspection) or the JPEG symbol tiles
         const h2j_scaled& sc = p.scaled[v];
         const size_t blocks = view_blocks(sc);
@@ -425,6 +453,36 @@ void build_finish_classes(ChunkPlan& p) {
     }
 }
 
+// K3c map: the raw outputs with their sources (what view() shows K4), by source class as K3u's (0: the 8-bit planes
+// K3s / K3r / K3p / K3u wrote; 1: another 8-bit source; 2: a 16-bit source), one launch per class present, its grid
+// as wide as the class's largest output needs
+void build_rgb_classes(ChunkPlan& p) {
+    for (size_t i = 0; i < p.rgbs.size(); i++) {
+        h2j_rgb& rec = p.rgbs[i];
+        const int v = p.rgbview[i];
+        const h2j_frame src = p.view(v);
+        rec.bit_depth = src.bit_depth;
+        rec.bit_depth_c = src.bit_depth_c;
+        rec.crop_x = src.crop_x;
+        rec.crop_y = src.crop_y;
+        rec.wide = (p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0) ? 1 : 0;
+        rec.src = src.pic2;
+        for (int c = 0; c < 3; c++) {
+            rec.src_stride[c] = src.pic_stride[c];
+            rec.src_off[c] = src.pic_off[c];
+        }
+    }
+    for (int cls = 0; cls < H2J_RGB_CLASSES && !p.rgbs.empty(); cls++) {
+        p.rgb_first[cls] = static_cast<int32_t>(p.rgbmap.size());
+        for (const h2j_rgb& rec : p.rgbs) {
+            if ((rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1) != cls) continue;
+            p.rgbmap.push_back(rec);
+            p.rgb_count[cls]++;
+            p.rgb_tiles[cls] = std::max(p.rgb_tiles[cls], h2j_k3c_tiles(rec.w, rec.h));
+        }
+    }
+}
+
 // the maps' places in the staging buffer, behind the records; with scaled pictures or several
 // renditions of a frame the JPEG source views of all frames and the K3s / K3r / K3p maps follow
 void layout_maps(ChunkPlan& p) {
@@ -448,6 +506,10 @@ void layout_maps(ChunkPlan& p) {
     if (!p.finmap.empty()) c.take(p.finmap.size() * sizeof(h2j_finish) + 16);
     p.at.qforce = c.off;  // only in chunks with a forced quantiser scale: one int32 a view
     if (p.qforced) c.take(static_cast<size_t>(p.nv) * 4 + 16);
+    p.at.rgb = c.off;  // only in chunks with raw outputs
+    if (!p.rgbmap.empty()) c.take(p.rgbmap.size() * sizeof(h2j_rgb) + 16);
+    p.at.jcompact = c.off;  // only in chunks with views that get no JPEG: the views K4 / K5 run on
+    if (p.compact()) c.take(static_cast<size_t>(p.njpeg) * sizeof(h2j_frame));
     p.at.bytes = c.off;
 }
 
@@ -473,7 +535,8 @@ void fill_descriptor(ChunkPlan& p) {
     // (a scaled picture: always K4a, on the scaled picture; K3s / K3r clears what K3 may have summed)
     // (a window: always K4a, on the window; a sharpened view: always K4a, on the sharpened planes)
     for (int v = 0; v < p.nv; v++)
-        d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v]) ? 0 : 1;
+        if (p.vjpeg[v])  // (K4 runs on the views that get a JPEG)
+            d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v]) ? 0 : 1;
 }
 
 }  // namespace
@@ -565,6 +628,10 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     for (auto* m : {&p.fins, &p.finmap}) m->clear();
     p.vqscale.clear();
     p.vsharpen.clear();
+    for (auto* m : {&p.rgbs, &p.rgbmap}) m->clear();
+    p.rgbview.clear();
+    p.vjpeg.clear();
+    for (int cls = 0; cls < H2J_RGB_CLASSES; cls++) p.rgb_first[cls] = p.rgb_count[cls] = p.rgb_tiles[cls] = 0;
     p.qforced = false;
     for (int cls = 0; cls < H2J_FINISH_CLASSES; cls++) p.fin_first[cls] = p.fin_count[cls] = p.fin_tiles[cls] = 0;
     p.fstat.assign(static_cast<size_t>(p.nf), 0);
@@ -577,6 +644,10 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     // scaled pictures present, or several renditions of a frame: a views array is uploaded
     p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; }) ||
               std::any_of(p.vsharpen.begin(), p.vsharpen.end(), [](int a) { return a != 0; });  // ... or a sharpened view
+    p.njpeg = static_cast<int>(std::count(p.vjpeg.begin(), p.vjpeg.end(), 1));
+    p.jviews.clear();
+    for (int v = 0; v < p.nv && p.compact(); v++)
+        if (p.vjpeg[v]) p.jviews.push_back(v);
     p.vjcoef.resize(static_cast<size_t>(p.nv));
     p.vfin.assign(static_cast<size_t>(p.nv), -1);
     layout_arena(p);
@@ -585,6 +656,7 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     build_scale_classes(p);
     build_orient_classes(p);
     build_finish_classes(p);
+    build_rgb_classes(p);
     layout_maps(p);
     fill_descriptor(p);
 }

@@ -31,6 +31,7 @@ struct ChunkPlan {
     std::vector<int> vfirst;         // per frame: its first view (nf + 1 entries)
     struct Rend {
         int out, view;  // index in the batch's output arrays; the view that holds its JPEG
+        int rgb;        // -1: the JPEG; else the raw output (rgbs) that holds its pixels
     };
     std::vector<Rend> rends;  // the chunk's renditions (those with valid options), frame-major
 
@@ -79,7 +80,27 @@ struct ChunkPlan {
     bool qforced = false;            // a view of the chunk forces its quantiser scale
     h2j_frame base_view(int v) const;  // view v without its sharpening: what K3u reads
 
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][jcoef][res][aux]
+    // RGB output (K3c): a rendition has a format; a raw one (RGB pixels instead of a file) is served by a view like any
+    // other -- the view of a JPEG rendition of the same frame with its (window, resolved output, sharpen) if there is
+    // one (the quantiser scale does not change the planes), else one of its own -- and has a record: K3c reads what
+    // view() shows K4 and writes the pixels into an arena region behind upic (256-byte aligned start per output, tight
+    // rows).  Renditions of one view with one layout share a record.  The region is what the chunk copies to the host
+    // beside the JPEG payloads.  A chunk without raw outputs has none of this and uploads what it always did
+    std::vector<h2j_rgb> rgbs;    // the chunk's raw outputs, view-major
+    std::vector<int> rgbview;     // per raw output: its view
+    std::vector<h2j_rgb> rgbmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_rgb), uploaded
+    int32_t rgb_first[H2J_RGB_CLASSES] = {0}, rgb_count[H2J_RGB_CLASSES] = {0}, rgb_tiles[H2J_RGB_CLASSES] = {0};
+    size_t rgb_base = 0, rgb_bytes = 0;  // the region: arena offset, bytes (whole 256-byte groups)
+    std::vector<char> vjpeg;      // per view: a JPEG rendition shows it (else raw ones only: its JPEG is never assembled)
+    int njpeg = 0;                // such views; 0: a chunk of raw renditions only, which runs no K4 / K5
+    // K4 / K5 run on the views some JPEG rendition shows.  Where that is not all of them (0 < njpeg < nv) those views
+    // are uploaded once more as an array of their own (jviews: their indices, in view order), which K4 / K5 take as
+    // their pictures, and the forced scales are packed for them: a view that only raw renditions show gets no JPEG,
+    // no payload in the pool and no share of the payload estimate
+    std::vector<int> jviews;
+    bool compact() const { return njpeg > 0 && njpeg < nv; }
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][rgb][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
     size_t seg_cap = 0;  // payload pool bytes (K5)
     int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)
@@ -94,7 +115,7 @@ struct ChunkPlan {
     // staging layout: byte offset of each array in the one buffer the chunk uploads
     struct Staging {
         size_t frames = 0, tus = 0, coefs = 0, ctbs = 0, slices = 0, sl = 0, k1map = 0, k1all = 0, sao = 0, k1map8 = 0,
-               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, finish = 0, qforce = 0, bytes = 0;
+               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, finish = 0, qforce = 0, rgb = 0, jcompact = 0, bytes = 0;
     } at;
 
     // the descriptor's scalar fields (counts, maxima, codec / sample-type masks, classes); its pointers,

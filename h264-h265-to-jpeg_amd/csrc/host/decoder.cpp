@@ -55,9 +55,11 @@ struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
     // the options of the picture's renditions: one (all 0: the decoded size; h2j_h265_to_jpeg_mem_scaled,
-    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3, _multi4, _multi5); per rendition the JPEG and status once the batch ran
-    std::vector<h2j_out_opts5> opts{h2j_out_opts5{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}}};
+    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3 .. _multi6); per rendition the JPEG (a raw rendition: its
+    // pixels), the output's size and status once the batch ran
+    std::vector<h2j_out_opts6> opts{h2j_out_opts6{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}}};
     std::vector<std::vector<uint8_t>> jpegs;
+    std::vector<int32_t> wh;
     std::vector<int> rstatus;
     int status = 0;  // of the first rendition, which is all a plain caller asks for (-1: the batch did not run)
     std::string error;
@@ -115,7 +117,7 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
 }
 
 // run one batch (caller holds no lock); fills jpegs / rstatus / status / error of each request.  Every
-// picture is decoded once (h2j_engine_transcode_multi5; a plain request is an item with one rendition)
+// picture is decoded once (h2j_engine_transcode_multi6; a plain request is an item with one rendition)
 void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
     if (n == 0) return;
@@ -123,7 +125,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<size_t> sizes(n);
     std::vector<int32_t> nrend(n);
     std::vector<int> base(n + 1, 0);
-    std::vector<h2j_out_opts5> opts;
+    std::vector<h2j_out_opts6> opts;
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
         const Request* q = batch[i];
@@ -137,21 +139,27 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int total = base[n];
     std::vector<size_t> off(total), len(total);
     std::vector<int> status(total);
+    std::vector<int32_t> wh(2 * static_cast<size_t>(total));
     std::vector<uint8_t> out;
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = h2j_engine_transcode_multi5(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
-                                       len.data(), status.data());
+        r = h2j_engine_transcode_multi6(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
+                                       len.data(), status.data(), wh.data());
         bool small = false;
-        for (int i = 0; i < total; i++) small = small || status[i] == -50;
+        size_t raw = 0;  // what the raw renditions need, exactly
+        for (int i = 0; i < total; i++) {
+            small = small || status[i] == -50;
+            if (opts[i].format) raw += 3 * static_cast<size_t>(wh[2 * i]) * static_cast<size_t>(wh[2 * i + 1]);
+        }
         if (!small) break;
-        cap *= 4;
+        cap = cap * 4 + raw;
     }
     for (int i = 0; i < n; i++) {
         Request* q = batch[i];
         q->jpegs.assign(static_cast<size_t>(nrend[i]), std::vector<uint8_t>());
         q->rstatus.assign(static_cast<size_t>(nrend[i]), 0);
+        q->wh.assign(wh.begin() + 2 * base[i], wh.begin() + 2 * base[i + 1]);
         for (int k = 0; k < nrend[i]; k++) {
             const int o = base[i] + k;
             int st = status[o];
@@ -281,14 +289,15 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
 }
 
-static h2j_out_opts5 opts5_of(const h2j_out_opts3& o) {
-    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0,
-                         {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
+static h2j_out_opts6 opts6_of(const h2j_out_opts3& o) {
+    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0, 0,
+                         {o.reserved[0], o.reserved[1], o.reserved[2]}};
 }
-static h2j_out_opts5 opts5_of(const h2j_out_opts2& o) {
-    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
+static h2j_out_opts6 opts6_of(const h2j_out_opts2& o) {
+    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
 }
-static h2j_out_opts5 opts5_of(const h2j_out_opts4& o) { return h2j::widen_opts4(o); }
+static h2j_out_opts6 opts6_of(const h2j_out_opts4& o) { return h2j::widen_opts5(h2j::widen_opts4(o)); }
+static h2j_out_opts6 opts6_of(const h2j_out_opts5& o) { return h2j::widen_opts5(o); }
 
 static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& opts, uint8_t** jpeg, size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
@@ -298,7 +307,7 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts[0] = opts5_of(opts);
+    req.opts[0] = opts6_of(opts);
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -326,33 +335,43 @@ extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int 
                                           size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    std::vector<h2j_out_opts5> o5;
-    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
+    std::vector<h2j_out_opts6> o6;
+    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi3(const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, uint8_t** jpeg,
                                            size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    std::vector<h2j_out_opts5> o5;
-    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
+    std::vector<h2j_out_opts6> o6;
+    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi4(const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, uint8_t** jpeg,
                                            size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    std::vector<h2j_out_opts5> o5;
-    for (int r = 0; r < nrend; r++) o5.push_back(opts5_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi5(data, size, nrend, o5.data(), jpeg, jpeg_len, status);
+    std::vector<h2j_out_opts6> o6;
+    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi5(const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, uint8_t** jpeg,
                                            size_t* jpeg_len, int* status) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (!opts) return -1;
+    std::vector<h2j_out_opts6> o6;
+    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
+    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_multi6(const uint8_t* data, size_t size, int nrend, const h2j_out_opts6* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status, int32_t* out_wh) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!jpeg || !jpeg_len || !status || !opts) return -1;
+    for (int r = 0; out_wh && r < 2 * nrend; r++) out_wh[r] = 0;
     for (int r = 0; r < nrend; r++) {
         jpeg[r] = nullptr;
         jpeg_len[r] = 0;
@@ -368,6 +387,7 @@ extern "C" int h2j_h265_to_jpeg_mem_multi5(const uint8_t* data, size_t size, int
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
     }
+    for (int r = 0; out_wh && r < 2 * nrend && r < static_cast<int>(req.wh.size()); r++) out_wh[r] = req.wh[r];
     for (int r = 0; r < nrend; r++) {
         status[r] = req.rstatus[r];
         if (status[r] != 0) continue;

@@ -50,6 +50,9 @@ extern "C" int h2j_gpu_orient(const h2j_gpu_batch*, const h2j_orient*, const int
 extern "C" int h2j_gpu_finish(const h2j_gpu_batch*, const h2j_finish*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 extern "C" int h2j_gpu_jpeg2(const h2j_gpu_batch*, const int32_t*, void*) __attribute__((weak));
+// likewise its RGB stage: K3c
+extern "C" int h2j_gpu_rgb(const h2j_gpu_batch*, const h2j_rgb*, const int32_t*, const int32_t*, const int32_t*, void*)
+    __attribute__((weak));
 
 namespace h2j {
 namespace {
@@ -185,49 +188,53 @@ int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
     return -100;
 }
 
-// Output options: h2j_out_opts5 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
+// Output options: h2j_out_opts6 is the engine's one option type (an h2j_out_opts item has the fit fields 0,
 // an h2j_out_opts2 item the crop fields, an h2j_out_opts3 item the orientation, an h2j_out_opts4 item qscale and
-// sharpen: widen_opts4 in job.h)
-const h2j_out_opts5 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};  // the JPEG at the decoded size
-std::vector<h2j_out_opts5> opts5_of(int n, const h2j_out_opts* o) {  // o null: all plain
-    std::vector<h2j_out_opts5> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+// sharpen, an h2j_out_opts5 item the format: widen_opts4, widen_opts5 in job.h)
+const h2j_out_opts6 kPlainOutput = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};  // the JPEG at the decoded size
+std::vector<h2j_out_opts6> opts6_of(int n, const h2j_out_opts* o) {  // o null: all plain
+    std::vector<h2j_out_opts6> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
     for (int i = 0; o && i < n; i++) {
         v[i].scale_log2 = o[i].scale_log2;
         v[i].max_dim = o[i].max_dim;
     }
     return v;
 }
-h2j_out_opts5 opts5_of(const h2j_out_opts4& o) { return widen_opts4(o); }
-h2j_out_opts5 opts5_of(const h2j_out_opts3& o) {
-    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0,
-                         {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
+h2j_out_opts6 opts6_of(const h2j_out_opts5& o) { return widen_opts5(o); }
+h2j_out_opts6 opts6_of(const h2j_out_opts4& o) { return widen_opts5(widen_opts4(o)); }
+h2j_out_opts6 opts6_of(const h2j_out_opts3& o) {
+    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0, 0,
+                         {o.reserved[0], o.reserved[1], o.reserved[2]}};
 }
-h2j_out_opts5 opts5_of(const h2j_out_opts2& o) {
-    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2], 0}};
+h2j_out_opts6 opts6_of(const h2j_out_opts2& o) {
+    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
 }
 template <typename T>
-std::vector<h2j_out_opts5> opts5_of(int n, const T* o) {  // h2j_out_opts2 / h2j_out_opts3 items
-    std::vector<h2j_out_opts5> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
-    for (int i = 0; o && i < n; i++) v[i] = opts5_of(o[i]);
+std::vector<h2j_out_opts6> opts6_of(int n, const T* o) {  // h2j_out_opts2 / h2j_out_opts3 items
+    std::vector<h2j_out_opts6> v(static_cast<size_t>(std::max(n, 0)), kPlainOutput);
+    for (int i = 0; o && i < n; i++) v[i] = opts6_of(o[i]);
     return v;
 }
-// the h2j_out_opts5 items of a multi call's h2j_out_opts2 / h2j_out_opts3 items (valid counts)
+// the h2j_out_opts6 items of a multi call's h2j_out_opts2 / h2j_out_opts3 items (valid counts)
 template <typename T>
-std::vector<h2j_out_opts5> multi_opts5(int n, const int32_t* nrend, const T* opts) {
+std::vector<h2j_out_opts6> multi_opts6(int n, const int32_t* nrend, const T* opts) {
     int total = 0;
     for (int i = 0; i < n; i++) total += nrend[i];
-    return opts5_of(total, opts);
+    return opts6_of(total, opts);
 }
-bool reserved_zero(const h2j_out_opts5& o) { return std::all_of(o.reserved, o.reserved + 4, [](int32_t r) { return r == 0; }); }
+bool reserved_zero(const h2j_out_opts6& o) { return std::all_of(o.reserved, o.reserved + 3, [](int32_t r) { return r == 0; }); }
 // finishing (include/h2j.h "Finishing"): a fixed quantiser scale, an unsharp mask
-bool finish_valid(const h2j_out_opts5& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
+bool finish_valid(const h2j_out_opts6& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
 bool finishing(const FrameJob::Output& o) { return o.qscale != 0 || o.sharpen != 0; }
+// RGB output (include/h2j.h "RGB output"): a known format, and no quantiser scale for pixels
+bool format_valid(const h2j_out_opts6& o) { return o.format >= H2J_FMT_JPEG && o.format <= H2J_FMT_RGB8_PLANAR && !(o.format && o.qscale); }
 // the orientation (0, 2..8) the options name for a picture whose display orientation SEI says sei_orient
-int resolve_orient(const h2j_out_opts5& o, int sei_orient) {
+int resolve_orient(const h2j_out_opts6& o, int sei_orient) {
     const int r = o.orient == H2J_ORIENT_AUTO ? sei_orient : o.orient;
     return r == 1 ? 0 : r;
 }
 const char kNoStageMessage[] = "the kernel library has no orientation stage (h2j_gpu_orient): oriented output needs a newer libh2j_hip.so";
+const char kNoRgbMessage[] = "the kernel library has no RGB stage (h2j_gpu_rgb): raw output needs a newer libh2j_hip.so";
 const char kNoFinishMessage[] = "the kernel library has no finishing stage (h2j_gpu_finish, h2j_gpu_jpeg2): qscale and sharpen need a newer libh2j_hip.so";
 // Scaled output (include/h2j.h h2j_out_opts): the scale of a w x h picture -- scale_log2, or with
 // max_dim > 0 the smallest k from scale_log2 up whose JPEG fits max_dim (3 if none does).
@@ -238,9 +245,9 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
 }
 // what can be said of the options before the picture's size is known (an item none of whose renditions
 // passes is not parsed); the window's place in the picture is checked by resolve_output
-bool out_opts_valid(const h2j_out_opts5& o) {
+bool out_opts_valid(const h2j_out_opts6& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o)) return false;
+    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o) || !format_valid(o)) return false;
     if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
     if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
         if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
@@ -249,7 +256,7 @@ bool out_opts_valid(const h2j_out_opts5& o) {
     if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts5& o, int w, int h) {
+int resolve_scale(const h2j_out_opts6& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
@@ -262,10 +269,11 @@ int resolve_scale(const h2j_out_opts5& o, int w, int h) {
 // resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest.
 // Orientation (include/h2j.h "Orientation"; sei_orient: the picture's, for H2J_ORIENT_AUTO) comes first: the
 // rule runs on the oriented size, the window is in the oriented picture
-FrameJob::Output resolve_output(const h2j_out_opts5& o, int W, int H, int sei_orient) {
+FrameJob::Output resolve_output(const h2j_out_opts6& o, int W, int H, int sei_orient) {
     FrameJob::Output out;
     out.qscale = o.qscale;
     out.sharpen = o.sharpen;
+    out.format = o.format;
     out.orient = resolve_orient(o, sei_orient);
     if (out.orient >= 5) std::swap(W, H);
     int64_t x = o.crop_x, y = o.crop_y, w = o.crop_w ? o.crop_w : W - x, h = o.crop_h ? o.crop_h : H - y;
@@ -306,7 +314,7 @@ FrameJob::Output resolve_output(const h2j_out_opts5& o, int W, int H, int sei_or
 }
 // W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
 // message they always got
-std::string out_opts_message(const h2j_out_opts5& o, int W = 0, int H = 0, int sei_orient = 0) {
+std::string out_opts_message(const h2j_out_opts6& o, int W = 0, int H = 0, int sei_orient = 0) {
     std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
@@ -318,6 +326,7 @@ std::string out_opts_message(const h2j_out_opts5& o, int W = 0, int H = 0, int s
     if (o.orient != 0) m += "; orient " + std::to_string(o.orient) + " (0..8, -1: the stream's display orientation)";
     if (o.qscale != 0 || o.sharpen != 0)
         m += "; qscale " + std::to_string(o.qscale) + " (0 or 2..31), sharpen " + std::to_string(o.sharpen) + " (0..64)";
+    if (o.format != 0) m += "; format " + std::to_string(o.format) + " (0 JPEG, 1 RGB, 2 planar RGB; not with qscale)";
     if (!(window && W > 0 && H > 0)) return m;
     const int ro = (o.orient >= H2J_ORIENT_AUTO && o.orient <= 8) ? resolve_orient(o, sei_orient) : 0;
     if (ro >= 5) std::swap(W, H);
@@ -326,10 +335,13 @@ std::string out_opts_message(const h2j_out_opts5& o, int W = 0, int H = 0, int s
     return m;
 }
 // the message of an output that failed with H2J_ERR_NO_STAGE: the stage the kernel library lacks
-const char* no_stage_message(const FrameJob::Output& o) { return (o.orient && !h2j_gpu_orient) ? kNoStageMessage : kNoFinishMessage; }
+const char* no_stage_message(const FrameJob::Output& o) {
+    if (o.orient && !h2j_gpu_orient) return kNoStageMessage;
+    return (finishing(o) && !(h2j_gpu_finish && h2j_gpu_jpeg2)) ? kNoFinishMessage : kNoRgbMessage;
+}
 // the outputs of a parsed job: every rendition's is resolved on its own, and invalid options fail that
 // rendition alone
-void resolve_outputs(const h2j_out_opts5* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts6* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
@@ -337,11 +349,12 @@ void resolve_outputs(const h2j_out_opts5* o, int nr, FrameJob& job) {
         else job.outs[r].error = H2J_ERR_OUT_OPTS;
         if (job.outs[r].error == 0 && job.outs[r].orient && !h2j_gpu_orient) job.outs[r].error = H2J_ERR_NO_STAGE;
         if (job.outs[r].error == 0 && finishing(job.outs[r]) && !(h2j_gpu_finish && h2j_gpu_jpeg2)) job.outs[r].error = H2J_ERR_NO_STAGE;
+        if (job.outs[r].error == 0 && job.outs[r].format && !h2j_gpu_rgb) job.outs[r].error = H2J_ERR_NO_STAGE;
     }
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts5* o, int nr, FrameJob& job, bool* ran) {
+int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts6* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -366,7 +379,7 @@ enum {
     EV_K1,
     EV_K2,
     EV_K3,
-    EV_SCALE,       // after K3o (oriented output) and K3s / K3r / K3p (scaled output)
+    EV_SCALE,       // after K3o (oriented output), K3s / K3r / K3p (scaled output), K3u (finishing) and K3c (RGB output)
     EV_K4,
     EV_K5,          // the last kernel: the other slot's next chunk waits for it
     EV_STATS,       // after the stats D2H
@@ -383,6 +396,8 @@ struct Slot {
     void* stream = nullptr;
     void* ev[EV_N] = {nullptr};
     size_t pay_pre = 0;        // payload bytes already copied in-stream by enqueue() (estimated, <= h_seg's capacity)
+    size_t raw_off = 0;        // h_seg: the chunk's RGB region (plan.rgb_bytes) in front, the payloads from here (0: no raw output)
+    bool raw_pre = false;      // the RGB region was copied in-stream by enqueue() (h_seg had room for it)
     int small_runs = 0;        // consecutive chunks whose payload used < 1/4 of h_seg (shrink after 8)
     size_t small_max = 0;      // the largest payload of that run
     DevBuf d_in, d_arena, d_seg, d_scratch;
@@ -419,7 +434,8 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3o + K3s + K3r + K3p
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_RAW_BYTES, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3o + K3s + K3r + K3p + K3u + K3c
+// ST_RAW_BYTES: bytes of the raw (RGB) renditions delivered; K3c's time counts in ST_SCALE
 // ST_RENDITIONS: JPEG outputs of the batch (ST_FRAMES: decoded pictures); ST_PARSED: pictures whose entropy decode ran
 
 struct ChunkTime {
@@ -438,7 +454,9 @@ struct Batch {
     size_t* out_off = nullptr;
     size_t* out_len = nullptr;
     int* status = nullptr;
-    std::vector<h2j_out_opts5> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    int32_t* out_wh = nullptr;                 // per rendition: its output's W, H (may be null)
+    size_t raw_planned = 0;                    // bytes of the raw renditions the chunks planned so far hold
+    std::vector<h2j_out_opts6> opts;           // output options per rendition, item-major (a plain item has one rendition)
     std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
     int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
@@ -591,7 +609,16 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
         put(p.at.orient, p.orientmap.data(), p.orientmap.size() * sizeof(h2j_orient));
         put(p.at.finish, p.finmap.data(), p.finmap.size() * sizeof(h2j_finish));
     }
-    if (p.qforced) put(p.at.qforce, p.vqscale.data(), static_cast<size_t>(p.nv) * 4);
+    if (p.qforced && !p.compact()) put(p.at.qforce, p.vqscale.data(), static_cast<size_t>(p.nv) * 4);
+    if (p.compact()) {  // the views K4 / K5 run on, and their forced scales, packed
+        h2j_frame* jc = reinterpret_cast<h2j_frame*>(hin + p.at.jcompact);
+        int32_t* qf = reinterpret_cast<int32_t*>(hin + p.at.qforce);
+        for (size_t i = 0; i < p.jviews.size(); i++) {
+            jc[i] = p.view(p.jviews[i]);
+            if (p.qforced) qf[i] = p.vqscale[p.jviews[i]];
+        }
+    }
+    put(p.at.rgb, p.rgbmap.data(), p.rgbmap.size() * sizeof(h2j_rgb));
     const std::vector<FrameJob>& jobs = *s.jobs;
     auto pack = [&](int k) {  // the frame's record ranges are where plan_chunk numbered them
         const FrameJob& j = jobs[s.live[k]];
@@ -643,6 +670,10 @@ void Engine::fill_descriptors(Slot& s) {
         jb.nframes = p.nv;
         jb.frames = jb.jframes = b.jframes;
     }
+    if (p.compact()) {  // ... and on those of them that get a JPEG, where some do not
+        jb.nframes = p.njpeg;
+        jb.frames = jb.jframes = reinterpret_cast<const h2j_frame*>(din + p.at.jcompact);
+    }
 }
 
 // upload, the kernels of s.stages, and the stats download, on the slot's stream
@@ -684,14 +715,23 @@ int Engine::launch(Slot& s, const Slot* after) {
         (!h2j_gpu_finish || h2j_gpu_finish(&b, reinterpret_cast<const h2j_finish*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.finish),
                                            p.fin_first, p.fin_count, p.fin_tiles, st)))
         return drain_fail(s, h2j_gpu_finish ? h2j_gpu_last_error() : kNoFinishMessage);
+    // K3c: only in chunks with raw outputs (likewise); out of place, K4 reads what it read
+    if (s.stages >= 3 && !p.rgbmap.empty() &&
+        (!h2j_gpu_rgb || h2j_gpu_rgb(&b, reinterpret_cast<const h2j_rgb*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.rgb),
+                                     p.rgb_first, p.rgb_count, p.rgb_tiles, st)))
+        return drain_fail(s, h2j_gpu_rgb ? h2j_gpu_last_error() : kNoRgbMessage);
     h2j_gpu_event_record(s.ev[EV_SCALE], st);
+    // a chunk of raw renditions only: nobody asked for a JPEG, so no K4 / K5 and no payload (the pool's byte count,
+    // which K5 would have written, is cleared instead)
+    const bool jpegs = p.njpeg > 0;
     // K4: through h2j_gpu_jpeg2 only in chunks with a forced quantiser scale (likewise)
-    if (s.stages >= 4 && p.qforced) {
+    if (s.stages >= 4 && jpegs && p.qforced) {
         if (!h2j_gpu_jpeg2 || h2j_gpu_jpeg2(&jb, reinterpret_cast<const int32_t*>(static_cast<const uint8_t*>(s.d_in.p) + p.at.qforce), st))
             return drain_fail(s, h2j_gpu_jpeg2 ? h2j_gpu_last_error() : kNoFinishMessage);
-    } else if (s.stages >= 4 && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    } else if (s.stages >= 4 && jpegs && h2j_gpu_jpeg(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K4], st);
-    if (s.entropy && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    if (s.entropy && jpegs && h2j_gpu_entropy(&jb, st)) return drain_fail(s, h2j_gpu_last_error());
+    if (s.entropy && !jpegs && h2j_gpu_memset(s.d_scratch.p, 0, 8, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K5], st);
     if (s.entropy) {
         r |= h2j_gpu_memcpy_d2h(s.h_js.p, s.d_scratch.p, 8, st);  // seg_total
@@ -719,15 +759,25 @@ int Engine::enqueue_payload_copy(Slot& s) {
         s.small_runs = 0;
     }
     s.pay_pre = 0;
-    if (s.entropy && s.h_seg.cap > 0) {
+    // raw outputs: the chunk's RGB region goes in front of the payloads, by the same copy policy -- in-stream when
+    // the pinned buffer already holds it (the plan knows its size), else in sync(), where the buffer grows
+    const size_t raw = s.entropy ? s.plan.rgb_bytes : 0;
+    s.raw_off = raw;
+    s.raw_pre = false;
+    if (s.entropy && s.h_seg.cap > raw) {
         // the copy is sized by the engine's payload-per-pixel estimate (1.3x, 4 KB
         // granules), not by the buffer's high-water mark: a small chunk after a 4K one moves its own
         // few MB, not the 4K chunk's 150 MB
         size_t want = s.plan.seg_cap;
         if (pay_per_px > 0) want = (static_cast<size_t>(1.3 * pay_per_px * s.plan.px) + 65536 + 4095) & ~static_cast<size_t>(4095);
-        s.pay_pre = std::min(std::min(s.h_seg.cap, s.plan.seg_cap), want);
+        s.pay_pre = s.plan.njpeg > 0 ? std::min(std::min(s.h_seg.cap - raw, s.plan.seg_cap), want) : 0;  // raw renditions only: no payload
         h2j_gpu_event_record(s.ev[EV_PAY_BEGIN], s.stream);
-        if (h2j_gpu_memcpy_d2h(s.h_seg.p, s.d_seg.p, s.pay_pre, s.stream))
+        if (raw) {
+            if (h2j_gpu_memcpy_d2h(s.h_seg.p, static_cast<uint8_t*>(s.d_arena.p) + s.plan.rgb_base, raw, s.stream))
+                return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
+            s.raw_pre = true;
+        }
+        if (s.pay_pre && h2j_gpu_memcpy_d2h(s.h_seg.p + raw, s.d_seg.p, s.pay_pre, s.stream))
             return drain_fail(s, std::string("download failed: ") + h2j_gpu_last_error());
         h2j_gpu_event_record(s.ev[EV_PAY_END], s.stream);
     }
@@ -760,25 +810,28 @@ int Engine::sync(Slot& s) {
         uint64_t total = 0;
         std::memcpy(&total, s.h_js.p, 8);
         stats[ST_PAY_BYTES] += static_cast<double>(total);
-        if (s.plan.px > 0) {  // payload per pixel: a running mean, never below the last chunk's
+        if (s.plan.px > 0 && s.plan.njpeg > 0) {  // payload per pixel: a running mean, never below the last chunk's
             const double ratio = static_cast<double>(total) / s.plan.px;
             pay_per_px = pay_per_px > 0 ? std::max(ratio, 0.7 * pay_per_px + 0.3 * ratio) : ratio;
         }
-        stats[ST_PAY_COPIED] += static_cast<double>(s.pay_pre);  // the in-stream copy, used or not
-        if (total > s.pay_pre) {  // not (all) copied in-stream: grow with headroom, copy it whole
+        stats[ST_PAY_COPIED] += static_cast<double>(s.pay_pre + (s.raw_pre ? s.raw_off : 0));  // the in-stream copy, used or not (the RGB region with it)
+        const size_t raw = s.raw_off;
+        if (total > s.pay_pre || (raw && !s.raw_pre)) {  // not (all) copied in-stream: grow with headroom, copy it whole
             const double tg = now_ms();
-            if (!s.h_seg.ensure(total + total / 4 + 16)) return fail("pinned host allocation failed");
+            if (!s.h_seg.ensure(raw + total + total / 4 + 16)) return fail("pinned host allocation failed");
             stats[ST_HOST_GROW] += now_ms() - tg;
-            stats[ST_PAY_COPIED] += static_cast<double>(total);
+            stats[ST_PAY_COPIED] += static_cast<double>(raw + total);
             pay_late = true;
             h2j_gpu_event_record(s.ev[EV_PAY2_BEGIN], s.stream);
-            if (h2j_gpu_memcpy_d2h(s.h_seg.p, s.d_seg.p, total, s.stream))
+            // (the RGB region again too: the buffer may be a new one)
+            if ((raw && h2j_gpu_memcpy_d2h(s.h_seg.p, static_cast<uint8_t*>(s.d_arena.p) + s.plan.rgb_base, raw, s.stream)) ||
+                (total && h2j_gpu_memcpy_d2h(s.h_seg.p + raw, s.d_seg.p, total, s.stream)))
                 return fail(std::string("download failed: ") + h2j_gpu_last_error());
             h2j_gpu_event_record(s.ev[EV_PAY2_END], s.stream);
         }
         // the pinned buffer shrinks after 8 chunks in a row that used less than a quarter of it
-        if (total * 4 < s.h_seg.cap) {
-            s.small_max = s.small_runs ? std::max(s.small_max, static_cast<size_t>(total)) : static_cast<size_t>(total);
+        if ((raw + total) * 4 < s.h_seg.cap) {
+            s.small_max = s.small_runs ? std::max(s.small_max, static_cast<size_t>(raw + total)) : static_cast<size_t>(raw + total);
             s.small_runs++;
         } else {
             s.small_runs = 0;
@@ -800,7 +853,7 @@ int Engine::sync(Slot& s) {
     const double d2h_stats = h2j_gpu_event_elapsed_ms(s.ev[EV_K5], s.ev[EV_STATS]);
     // both payload copies when the in-stream one fell short (the second one's events had
     // overwritten the first's)
-    const double d2h_pay = (s.entropy && s.pay_pre ? h2j_gpu_event_elapsed_ms(s.ev[EV_PAY_BEGIN], s.ev[EV_PAY_END]) : 0.0) +
+    const double d2h_pay = (s.entropy && (s.pay_pre || s.raw_pre) ? h2j_gpu_event_elapsed_ms(s.ev[EV_PAY_BEGIN], s.ev[EV_PAY_END]) : 0.0) +
                            (pay_late ? h2j_gpu_event_elapsed_ms(s.ev[EV_PAY2_BEGIN], s.ev[EV_PAY2_END]) : 0.0);
     stats[ST_D2H] += d2h_stats + d2h_pay;
     stats[ST_D2H_STATS] += d2h_stats;
@@ -888,6 +941,10 @@ static double hbm_estimate(const FrameJob& j) {
         est += 1.5 * (o.scale_log2 == H2J_SCALE_RESAMPLE ? static_cast<double>(o.fit_w) * o.fit_h
                                                            : static_cast<double>(o.win_w) * o.win_h / (1 << 2 * o.scale_log2)) + 4096;
     }
+    // raw outputs: the pixels K3c writes (3 B per output sample; one that shares a JPEG rendition's view added that
+    // view's regions above for nothing: an overestimate)
+    for (int r = 0; r < j.nouts; r++)
+        if (j.outs[r].error == 0 && j.outs[r].format) est += 3.0 * j.outs[r].out_w() * j.outs[r].out_h() + 4096;
     return est;
 }
 // JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
@@ -1007,9 +1064,11 @@ int Engine::run_batch(Batch& b) {
         const int nf = p.nf, nv = p.nv, nr = static_cast<int>(p.rends.size());
         const uint8_t* js = s.h_js.p + 256;
         std::vector<size_t> sz(nv);  // per view: its JPEG, encoded once
+        const uint8_t* pay = s.h_seg.p + s.raw_off;  // the payloads, behind the chunk's RGB region (raw outputs)
         auto size_of = [&](int k) {
             const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * p.jstat_stride);
-            sz[k] = st->seg_off == ~0ull ? 0 : jpeg_container_size(*st, s.h_seg.p + st->seg_off, kLavcIdent);
+            // (a view that only raw renditions show: K4 / K5 made a JPEG of it that nobody asked for; it is not assembled)
+            sz[k] = (st->seg_off == ~0ull || !p.vjpeg[k]) ? 0 : jpeg_container_size(*st, pay + st->seg_off, kLavcIdent);
         };
         par(nv, size_of);
         // every rendition gets its place in the output; renditions of one view (the same resolved output)
@@ -1026,34 +1085,45 @@ int Engine::run_batch(Batch& b) {
                 rc = -3;
                 continue;
             }
-            if (!sz[k]) {
+            const int g = p.rends[q].rgb;  // a raw rendition: 3 W H pixel bytes from the chunk's RGB region
+            const size_t len = g >= 0 ? 3 * static_cast<size_t>(p.rgbs[g].w) * p.rgbs[g].h : sz[k];
+            if (!len) {
                 status[i] = -51;  // payload pool overflow
                 rc = -3;
                 continue;
             }
-            if (pos + sz[k] > b.out_cap) {
+            if (pos + len > b.out_cap) {
                 status[i] = -50;
                 rc = -3;
                 continue;
             }
             at[q] = pos;
-            if (first[k] < 0) first[k] = q;
+            if (g < 0 && first[k] < 0) first[k] = q;
             b.out_off[i] = pos;
-            b.out_len[i] = sz[k];
-            pos += sz[k];
+            b.out_len[i] = len;
+            pos += len;
         }
         auto write = [&](int k) {
             if (first[k] < 0) return;
             const h2j_jstat* st = reinterpret_cast<const h2j_jstat*>(js + k * p.jstat_stride);
             const h2j_scaled& sc = p.scaled[k];
-            jpeg_write_container(*st, s.h_seg.p + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[first[k]]);
+            jpeg_write_container(*st, pay + st->seg_off, sc.jpeg_w, sc.jpeg_h, kLavcIdent, b.out + at[first[k]]);
         };
         par(nv, write);
-        if (nr > nv)
+        if (nr > nv || !p.rgbs.empty())
             for (int q = 0; q < nr; q++) {
                 const int k = p.rends[q].view;
-                if (at[q] != ~static_cast<size_t>(0) && first[k] != q) std::memcpy(b.out + at[q], b.out + at[first[k]], sz[k]);
+                if (p.rends[q].rgb < 0 && at[q] != ~static_cast<size_t>(0) && first[k] != q) std::memcpy(b.out + at[q], b.out + at[first[k]], sz[k]);
             }
+        if (!p.rgbs.empty()) {  // the raw renditions' pixels: from the pinned buffer to their places
+            par(nr, [&](int q) {
+                const int g = p.rends[q].rgb;
+                if (g < 0 || at[q] == ~static_cast<size_t>(0)) return;
+                std::memcpy(b.out + at[q], s.h_seg.p + (p.rgbs[g].dst_off - p.rgb_base), b.out_len[p.rends[q].out]);
+            });
+            for (int q = 0; q < nr; q++)
+                if (p.rends[q].rgb >= 0 && at[q] != ~static_cast<size_t>(0)) stats[ST_RAW_BYTES] += static_cast<double>(b.out_len[p.rends[q].out]);
+        }
         stats[ST_ASSEMBLE] += now_ms() - ta;
         stats[ST_RENDITIONS] += nr;
         stats[ST_FRAMES] += nf;
@@ -1108,8 +1178,29 @@ int Engine::run_batch(Batch& b) {
                     jobs[k].message = "field picture (PAFF): no frame from one field (H2J_STRICT_REFERENCE)";
                 }
                 // a failed item fails every rendition; else each rendition's own options decide
-                for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++)
-                    status[o] = jobs[k].error ? jobs[k].error : jobs[k].outs[o - b.rbase[k]].error;
+                for (int o = b.rbase[k]; o < b.rbase[k + 1]; o++) {
+                    if (jobs[k].error) {
+                        status[o] = jobs[k].error;
+                        continue;
+                    }
+                    FrameJob::Output& jo = jobs[k].outs[o - b.rbase[k]];
+                    if (b.out_wh && jo.error != H2J_ERR_OUT_OPTS) {  // the options resolved: the output's size
+                        b.out_wh[2 * o] = jo.out_w();
+                        b.out_wh[2 * o + 1] = jo.out_h();
+                    }
+                    // a raw rendition's size is known here: one that cannot fit the output buffer behind the raw
+                    // renditions planned before it (JPEGs only take more) fails now, and K3c does not run for it
+                    if (jo.error == 0 && jo.format) {
+                        const size_t len = 3 * static_cast<size_t>(jo.out_w()) * jo.out_h();
+                        if (b.raw_planned + len > b.out_cap) {
+                            jo.error = -50;
+                            rc = -3;
+                        } else {
+                            b.raw_planned += len;
+                        }
+                    }
+                    status[o] = jo.error;
+                }
                 // a parsed item none of whose renditions is valid (every window outside the picture) has no
                 // view: it gets no frame in the chunk, its renditions have their statuses
                 bool any_output = false;
@@ -1196,8 +1287,8 @@ const char* h2j_engine_error(h2j_engine* e) { return e ? e->e.err.c_str() : "no 
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts5* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
-                            int* status, bool latency) {
+                            const h2j_out_opts6* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            int* status, bool latency, int32_t* out_wh = nullptr) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
     b->n = n;
@@ -1208,6 +1299,7 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     b->out_off = out_off;
     b->out_len = out_len;
     b->status = status;
+    b->out_wh = out_wh;
     b->rbase.assign(static_cast<size_t>(n) + 1, 0);
     for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + (nrend ? nrend[i] : 1);
     b->nout = b->rbase[n];
@@ -1217,6 +1309,7 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
         out_len[i] = 0;
         out_off[i] = 0;
         status[i] = 0;
+        if (out_wh) out_wh[2 * i] = out_wh[2 * i + 1] = 0;
     }
     b->bounds = latency ? h2j::chunk_bounds(n) : h2j::chunk_bounds_throughput(n);
     const int nchunks = static_cast<int>(b->bounds.size()) - 1;
@@ -1248,14 +1341,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::opts5_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::opts6_of(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts5_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts6_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -1288,7 +1381,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts5_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::opts6_of(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1296,7 +1389,7 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts5_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, opts ? h2j::opts6_of(n, opts).data() : nullptr, out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1313,7 +1406,7 @@ int64_t h2j_engine_submit_multi(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1321,7 +1414,7 @@ int64_t h2j_engine_submit_multi3(h2j_engine* w, int n, const uint8_t* const* dat
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_multi5(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1329,7 +1422,24 @@ int64_t h2j_engine_submit_multi5(h2j_engine* w, int n, const uint8_t* const* dat
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+}
+
+int64_t h2j_engine_submit_multi6(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                 const h2j_out_opts6* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                 int* status, int32_t* out_wh) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    return submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, false, out_wh);
+}
+
+int h2j_engine_transcode_multi6(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
+                                const h2j_out_opts6* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                                int* status, int32_t* out_wh) {
+    if (!w) return -1;
+    if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, true, out_wh);
+    return h2j_engine_wait(w, t);
 }
 
 int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1337,7 +1447,7 @@ int h2j_engine_transcode_multi(h2j_engine* w, int n, const uint8_t* const* data,
                                int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1346,7 +1456,7 @@ int h2j_engine_transcode_multi3(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1355,7 +1465,7 @@ int h2j_engine_transcode_multi5(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -1364,7 +1474,7 @@ int64_t h2j_engine_submit_multi4(h2j_engine* w, int n, const uint8_t* const* dat
                                  int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
@@ -1372,21 +1482,21 @@ int h2j_engine_transcode_multi4(h2j_engine* w, int n, const uint8_t* const* data
                                 int* status) {
     if (!w) return -1;
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts5(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::multi_opts6(n, nrend, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
 int h2j_crop_window4(int w, int h, const h2j_out_opts4* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
     if (!o) return H2J_ERR_OUT_OPTS;
-    const h2j_out_opts5 o5 = h2j::opts5_of(*o);
-    return h2j_crop_window5(w, h, &o5, sei_orient, win, ow, oh, orient);
+    const h2j_out_opts6 o6 = h2j::opts6_of(*o);
+    return h2j_crop_window6(w, h, &o6, sei_orient, win, ow, oh, orient);
 }
 
 int h2j_crop_window(int w, int h, const h2j_out_opts3* o, int32_t* win, int* ow, int* oh) {
     if (!o) return H2J_ERR_OUT_OPTS;
-    const h2j_out_opts5 o5 = h2j::opts5_of(*o);
+    const h2j_out_opts6 o6 = h2j::opts6_of(*o);
     int orient = 0;
-    return h2j_crop_window5(w, h, &o5, 0, win, ow, oh, &orient);
+    return h2j_crop_window6(w, h, &o6, 0, win, ow, oh, &orient);
 }
 
 int h2j_stream_orientation(const uint8_t* data, size_t size) {
@@ -1397,6 +1507,12 @@ int h2j_stream_orientation(const uint8_t* data, size_t size) {
 }
 
 int h2j_crop_window5(int w, int h, const h2j_out_opts5* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
+    if (!o) return H2J_ERR_OUT_OPTS;
+    const h2j_out_opts6 o6 = h2j::opts6_of(*o);
+    return h2j_crop_window6(w, h, &o6, sei_orient, win, ow, oh, orient);
+}
+
+int h2j_crop_window6(int w, int h, const h2j_out_opts6* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
     if (!o || !win || !ow || !oh || !orient || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
         sei_orient > 8 || !h2j::out_opts_valid(*o))
         return H2J_ERR_OUT_OPTS;
@@ -1407,9 +1523,8 @@ int h2j_crop_window5(int w, int h, const h2j_out_opts5* o, int sei_orient, int32
     win[1] = out.win_y;
     win[2] = out.win_w;
     win[3] = out.win_h;
-    const bool resample = out.scale_log2 == H2J_SCALE_RESAMPLE;
-    *ow = resample ? out.fit_w : h2j_scaled_dim(out.win_w, out.scale_log2);
-    *oh = resample ? out.fit_h : h2j_scaled_dim(out.win_h, out.scale_log2);
+    *ow = out.out_w();
+    *oh = out.out_h();
     return 0;
 }
 
@@ -1435,7 +1550,7 @@ int h2j_fit_size(int w, int h, int fit_w, int fit_h, int flags, int* ow, int* oh
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts5* o = &h2j::kPlainOutput, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts6* o = &h2j::kPlainOutput, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -1543,7 +1658,7 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
 // (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too; 12: qscale and sharpen too)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts5* o, int nrend, int pick,
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts6* o, int nrend, int pick,
                               uint8_t* planes_out, size_t cap, int* info, int info_n = 4) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
@@ -1625,13 +1740,13 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts5 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};
+    const h2j_out_opts6 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts5 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};
+    const h2j_out_opts6 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
@@ -1639,28 +1754,28 @@ int h2j_engine_decode_multi(h2j_engine* w, const uint8_t* data, size_t size, int
                             uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
+    return decode_jpeg_source(w, data, size, h2j::opts6_of(nrend, opts).data(), nrend, pick, planes_out, cap, info);
 }
 
 int h2j_engine_decode_multi3(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 8);
+    return decode_jpeg_source(w, data, size, h2j::opts6_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 8);
 }
 
 int h2j_engine_decode_multi5(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (pick < 0 || pick >= nrend) return -1;
-    return decode_jpeg_source(w, data, size, opts, nrend, pick, planes_out, cap, info, 12);
+    if (pick < 0 || pick >= nrend || !opts) return -1;
+    return decode_jpeg_source(w, data, size, h2j::opts6_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 12);
 }
 
 int h2j_engine_decode_multi4(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, int pick,
                              uint8_t* planes_out, size_t cap, int* info) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::opts5_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 10);
+    return decode_jpeg_source(w, data, size, h2j::opts6_of(nrend, opts).data(), nrend, pick, planes_out, cap, info, 10);
 }
 
 int h2j_engine_host_info(h2j_engine* w, int* out, int n) {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "h2j.h"
+#include "h2j_gpu.h"
 #include "h2j_jobs.h"
 
 namespace h2j {
@@ -48,6 +49,12 @@ struct FrameJob {
         // finishing (include/h2j.h "Finishing"): the quantiser scale K4 is to use (0: the rate control's) and the
         // strength of the unsharp mask K3u applies to the output's 8-bit luma (0: none)
         int qscale = 0, sharpen = 0;
+        // RGB output (include/h2j.h "RGB output"): 0 the JPEG; H2J_FMT_RGB8 / H2J_FMT_RGB8_PLANAR: the output's final
+        // 8-bit planes as RGB pixels, made by K3c
+        int format = 0;
+        // the output's luma size: the window's at the resolved scale, or the fit size
+        int out_w() const { return scale_log2 == H2J_SCALE_RESAMPLE ? fit_w : h2j_scaled_dim(win_w, scale_log2); }
+        int out_h() const { return scale_log2 == H2J_SCALE_RESAMPLE ? fit_h : h2j_scaled_dim(win_h, scale_log2); }
     };
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;
@@ -75,6 +82,13 @@ struct FrameJob {
 inline h2j_out_opts5 widen_opts4(const h2j_out_opts4& o) {
     return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient, 0, 0,
                          {o.reserved[0] | o.reserved[1] | o.reserved[2], o.reserved[3], o.reserved[4], o.reserved[5]}};
+}
+
+// ... and h2j_out_opts6 took one more word (format) from h2j_out_opts5, in the same way: the engine's one option type
+// is now h2j_out_opts6, and an h2j_out_opts5 item is the one with format 0
+inline h2j_out_opts6 widen_opts5(const h2j_out_opts5& o) {
+    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
+                         o.qscale, o.sharpen, 0, {o.reserved[0] | o.reserved[1], o.reserved[2], o.reserved[3]}};
 }
 
 // Offsets of the scaling-factor tables inside FrameJob::sl

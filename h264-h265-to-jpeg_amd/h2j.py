@@ -56,6 +56,17 @@ class OutOpts5(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 4)]
 
 
+class OutOpts6(ctypes.Structure):
+    """include/h2j.h h2j_out_opts6: h2j_out_opts5 and the pixel format (the JPEG, or raw RGB made on the GPU)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("orient", ctypes.c_int32), ("qscale", ctypes.c_int32), ("sharpen", ctypes.c_int32),
+                ("format", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+FMT_JPEG, FMT_RGB8, FMT_RGB8_PLANAR = 0, 1, 2  # include/h2j.h H2J_FMT_*
+FORMATS = {"jpeg": FMT_JPEG, "rgb": FMT_RGB8, "rgb_planar": FMT_RGB8_PLANAR}  # the spec key "format"
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
 FIT_COVER = 2  # include/h2j.h H2J_FIT_COVER
 ERR_OUT_OPTS = -60  # include/h2j.h H2J_ERR_OUT_OPTS: status of an item with invalid output options
@@ -206,6 +217,21 @@ def load_library() -> ctypes.CDLL:
         lib.h2j_crop_window5.restype = ctypes.c_int
         lib.h2j_crop_window5.argtypes = [ctypes.c_int, ctypes.c_int, opt5p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    # RGB output (raw renditions): likewise absent from an older build
+    if hasattr(lib, "h2j_engine_transcode_multi6"):
+        opt6p = ctypes.POINTER(OutOpts6)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi6.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi6.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt6p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_engine_submit_multi6.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi6.argtypes = lib.h2j_engine_transcode_multi6.argtypes
+        lib.h2j_h265_to_jpeg_mem_multi6.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi6.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt6p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_crop_window6.restype = ctypes.c_int
+        lib.h2j_crop_window6.argtypes = [ctypes.c_int, ctypes.c_int, opt6p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -236,7 +262,7 @@ def _u8(buf: bytes):
 STAT_KEYS = ["parse_ms", "h2d_ms", "recon_ms", "deblock_ms", "sao_ms", "jpeg_ms", "d2h_ms",
              "assemble_ms", "total_ms", "frames", "alg_bytes", "entropy_ms", "prep_ms", "chunks", "pack_ms",
              "parse_run_ms", "d2h_stats_ms", "d2h_payload_ms", "payload_bytes", "host_grow_ms", "h2d_bytes",
-             "payload_copied_bytes", "scale_ms", "renditions", "parsed"]
+             "payload_copied_bytes", "scale_ms", "renditions", "parsed", "raw_bytes"]
 
 
 def _per_item(v, n, name):
@@ -293,7 +319,16 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen", "format")
+
+
+def _format_value(v, what):
+    """A pixel format as h2j_out_opts6 takes it: "jpeg", "rgb" or "rgb_planar" (None: the JPEG)."""
+    if v is None:
+        return FMT_JPEG
+    if isinstance(v, str) and v in FORMATS:
+        return FORMATS[v]
+    raise ValueError(f'{what}: format {v!r} is not "jpeg", "rgb" or "rgb_planar"')
 
 
 def _finish_value(v, what, name):
@@ -324,7 +359,8 @@ def rendition_spec(spec):
     """One rendition spec -> (scale_log2, max_dim, fit_w, fit_h, flags), the fields of h2j_out_opts2; with
     a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3; with an orient
     key those and orient: the fields of h2j_out_opts4; with a qscale or sharpen key those (orient 0 if the spec
-    names none), qscale and sharpen: the fields of h2j_out_opts5.
+    names none), qscale and sharpen: the fields of h2j_out_opts5; with a format key those (0 where the spec names
+    none) and format: the fields of h2j_out_opts6.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
     of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
@@ -333,7 +369,9 @@ def rendition_spec(spec):
     the stream's display orientation SEI names; crop, cover, scale and fit then act on the oriented
     picture), qscale (2..31: the JPEG quantiser scale instead of the rate control's; 0: the rate control's) and
     sharpen (1..64: an unsharp mask of strength sharpen / 16 on the luma of the rendition's final 8-bit planes;
-    0: none).  Values are not range-checked here: the engine fails a rendition
+    0: none) and format ("jpeg": the file, as without the key; "rgb": the rendition's final picture as 8-bit RGB
+    pixels, numpy (H, W, 3); "rgb_planar": the same as (3, H, W) -- converted on the GPU, no JPEG loss).
+    Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
         raise ValueError(f"rendition {spec!r}: an int (scale), a (w, h) pair (fit) or a dict")
@@ -344,7 +382,11 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format)")
+        if "format" in spec:  # the h2j_out_opts6 fields, whatever else the spec names
+            rest = dict(spec)
+            fmt = _format_value(rest.pop("format"), f"rendition {spec!r}")
+            return (tuple(rendition_spec(rest)) + (0,) * 7)[:12] + (fmt,)
         if "qscale" in spec or "sharpen" in spec:  # the h2j_out_opts5 fields, whatever else the spec names
             rest = dict(spec)
             q = _finish_value(rest.pop("qscale", None), f"rendition {spec!r}", "qscale")
@@ -415,9 +457,12 @@ def _multi_cap(streams, per_item, floor):
     cap = 0
     for s, specs in zip(streams, per_item):
         full = max(floor, 4 * len(s))
-        for scale, max_dim, fw, fh, *_ in specs:
+        for spec in specs:
+            scale, max_dim, fw, fh = spec[:4]
             plain_scale = 0 <= scale <= 3 and not (max_dim or fw or fh)
             cap += (full >> scale) + 65536 if plain_scale else full
+            if len(spec) > 12 and spec[12] and fw > 0 and fh > 0:
+                cap += 3 * fw * fh  # raw pixels of a boxed output: never more than the box (any other: the retry sizes it)
     return cap
 
 
@@ -427,7 +472,9 @@ def _multi_opts(per_item):
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    if any(len(t) > 10 for t in flat):  # a finishing option: the multi5 calls
+    if any(len(t) > 12 for t in flat):  # a format: the multi6 calls
+        opts = (OutOpts6 * len(flat))(*[OutOpts6(*(tuple(t) + (0,) * 8)[:13]) for t in flat])
+    elif any(len(t) > 10 for t in flat):  # a finishing option: the multi5 calls
         opts = (OutOpts5 * len(flat))(*[OutOpts5(*(tuple(t) + (0,) * 7)[:12]) for t in flat])
     elif any(len(t) > 9 for t in flat):  # an orientation: the multi4 calls
         opts = (OutOpts4 * len(flat))(*[OutOpts4(*(tuple(t) + (0,) * 5)[:10]) for t in flat])
@@ -477,8 +524,18 @@ def _per_item_finish(v, n, name):
     return [None if x is None else _finish_value(x, name, name) for x in v]
 
 
-def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None):
-    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale or sharpen is given."""
+def _per_item_format(v, n):
+    """format (None, one name for every item, or a per-item sequence of names or None) -> n names or None."""
+    if v is None or isinstance(v, str):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"format: {len(v)} entries for {n} streams")
+    return v
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None, format=None):
+    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale, sharpen or format is given."""
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
     ft = [None] * n if fit is None else _per_item_fit(fit, n)
     if isinstance(stretch, (bool, np.bool_)) or stretch is None:
@@ -491,6 +548,7 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
     cv = _per_item_shape(cover, n, "cover", _is_pair, "a (w, h) pair")
     orr = _per_item_orient(orient, n)
     qs, sh = _per_item_finish(qscale, n, "qscale"), _per_item_finish(sharpen, n, "sharpen")
+    fm = _per_item_format(format, n)
     out = []
     for i in range(n):
         d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
@@ -506,6 +564,8 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
             d["qscale"] = qs[i]
         if sh[i] is not None:
             d["sharpen"] = sh[i]
+        if fm[i] is not None:
+            d["format"] = fm[i]
         out.append([d])
     return out
 
@@ -603,7 +663,7 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -627,12 +687,15 @@ class Engine:
 
         qscale (2..31: that JPEG quantiser scale instead of the rate control's) and sharpen (1..64: an unsharp
         mask of strength sharpen / 16 on the output's luma, on the GPU) (h2j_out_opts5): an int for every item
-        or a per-item sequence of ints or None."""
+        or a per-item sequence of ints or None.
+
+        format ("jpeg", "rgb", "rgb_planar"; h2j_out_opts6): one name for every item or a per-item sequence of names
+        or None; the entry of a raw item is a numpy uint8 array, (H, W, 3) or (3, H, W), instead of bytes."""
         n = len(streams)
         if n == 0:
             return []
-        if any(v is not None for v in (crop, cover, orient, qscale, sharpen)):  # one rendition per item through the multi3 / multi4 / multi5 call
-            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen))
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format)):  # one rendition per item through the multi3 .. multi6 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format))
             self.last_status = [st[0] for st in self.last_status]
             return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
@@ -667,37 +730,63 @@ class Engine:
 
         renditions: one list of specs for every item, or one such list per item (normalize_renditions);
         a spec is an int (scale), a (w, h) tuple (fit) or a dict with any of scale, max_dim, fit,
-        stretch, crop, cover (rendition_spec).  last_status has the result's shape.  out_cap: the output buffer size tried first
-        (0: an estimate); renditions that did not fit (-50) make the call retry with a larger one."""
+        stretch, crop, cover, orient, qscale, sharpen, format (rendition_spec).  The entry of a raw rendition (format "rgb" /
+        "rgb_planar") is a numpy uint8 array, (H, W, 3) / (3, H, W).  last_status has the result's shape.  out_cap: the
+        output buffer size tried first (0: an estimate); renditions that did not fit (-50) make the call retry with a
+        larger one -- raw renditions are then sized exactly, from the sizes the first pass reported."""
         n = len(streams)
         per_item = normalize_renditions(renditions, n)
         if n == 0:
             self.last_status = []
             return []
+        return self._transcode_specs(streams, per_item, out_cap)
+
+    def _transcode_specs(self, streams, per_item, out_cap=0):
+        """transcode_multi with the renditions already normalised (normalize_renditions' result)."""
+        n = len(streams)
         nrend, opts, total = _multi_opts(per_item)
         bufs = [_u8(s) for s in streams]
         ptrs = (ctypes.POINTER(ctypes.c_uint8) * n)(*[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         cap = int(out_cap) or _multi_cap(streams, per_item, 1 << 20)
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
+        wh = (ctypes.c_int32 * (2 * total))() if opts._type_ is OutOpts6 else None  # the multi6 call reports the sizes
+        jpeg_cap = cap
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            call = {OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
+            call = {OutOpts6: "h2j_engine_transcode_multi6", OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
             call = getattr(self._lib, call)
-            rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
-            if not any(status[i] == -50 for i in range(total)):
+            rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
+            small = [i for i in range(total) if status[i] == -50]
+            if not small:
                 break
-            cap *= 4
+            if wh is None:
+                cap *= 4
+            else:  # raw renditions: exactly what they need; the JPEGs' share grows only if one of them did not fit
+                raw = sum(3 * wh[2 * i] * wh[2 * i + 1] for i in range(total) if opts[i].format)
+                if raw == 0 or any(not opts[i].format for i in small) or jpeg_cap + raw <= cap:
+                    jpeg_cap *= 4
+                cap = jpeg_cap + raw
         if rc < 0 and rc != -3:
             raise RuntimeError(f"h2j_engine_transcode_multi failed ({rc}): {self.error()}")
-        return self._multi_result(per_item, out, offs, lens, status)
+        return self._multi_result(per_item, out, offs, lens, status, wh)
 
-    def _multi_result(self, per_item, out, offs, lens, status):
+    def _multi_result(self, per_item, out, offs, lens, status, wh=None):
         mv = memoryview(out)
+
+        def entry(o, spec):
+            if status[o] != 0:
+                return None
+            fmt = spec[12] if len(spec) > 12 else FMT_JPEG
+            if fmt == FMT_JPEG:
+                return bytes(mv[offs[o]:offs[o] + lens[o]])
+            w, h = int(wh[2 * o]), int(wh[2 * o + 1])
+            px = np.frombuffer(out, dtype=np.uint8, count=int(lens[o]), offset=int(offs[o]))
+            return px.reshape((h, w, 3) if fmt == FMT_RGB8 else (3, h, w)).copy()
+
         res, st, o = [], [], 0
         for specs in per_item:
-            res.append([bytes(mv[offs[o + r]:offs[o + r] + lens[o + r]]) if status[o + r] == 0 else None
-                        for r in range(len(specs))])
+            res.append([entry(o + r, specs[r]) for r in range(len(specs))])
             st.append([int(status[o + r]) for r in range(len(specs))])
             o += len(specs)
         self.last_status = st
@@ -706,12 +795,14 @@ class Engine:
     def transcode_multi_async(self, batches: Sequence[Sequence[bytes]], renditions) -> List[List[List[Optional[bytes]]]]:
         """transcode_multi for several batches through the asynchronous path, all submitted before the
         first wait; renditions as in transcode_multi, for every batch (per-item lists: one per item of
-        each batch, so the batches then have the same length)."""
+        each batch, so the batches then have the same length).  A raw rendition's size is the picture's, unknown before
+        the parse: the items of raw renditions that did not fit the first buffer are run once more, synchronously, with
+        a buffer sized from the sizes the first pass reported."""
         return self._multi_async(batches, [renditions] * len(batches))
 
     def _multi_async(self, batches, renditions_of):
         """transcode_multi_async with the renditions of each batch."""
-        held, tickets = [], []
+        held, tickets, streams_of = [], [], [list(b) for b in batches]
         for streams, renditions in zip(batches, renditions_of):
             n = len(streams)
             per_item = normalize_renditions(renditions, n)
@@ -722,10 +813,11 @@ class Engine:
             cap = _multi_cap(streams, per_item, 2 << 20)
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
-            held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item))
-            call = {OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
+            wh = (ctypes.c_int32 * (2 * total))() if opts._type_ is OutOpts6 else None
+            held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item, wh))
+            call = {OutOpts6: "h2j_engine_submit_multi6", OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
             call = getattr(self._lib, call)
-            t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status)
+            t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
             if t <= 0:
                 raise RuntimeError(f"h2j_engine_submit_multi failed ({t})")
             tickets.append(t)
@@ -734,8 +826,26 @@ class Engine:
             rc = self.wait(t)
             if rc < 0 and rc != -3:
                 raise RuntimeError(f"h2j_engine_wait failed ({rc}): {self.error()}")
-            res.append(self._multi_result(h[9], h[5], h[6], h[7], h[8]))
-            sts.append(self.last_status)
+            out = self._multi_result(h[9], h[5], h[6], h[7], h[8], h[10])
+            st = self.last_status
+            # raw renditions that did not fit the estimate (their size is the picture's, unknown before the parse): their
+            # items once more, synchronously, the buffer sized from the sizes this pass reported
+            again = [i for i, row in enumerate(st) if -50 in row] if h[10] is not None else []
+            if again:
+                base = [0]
+                for specs in h[9]:
+                    base.append(base[-1] + len(specs))
+                wh, cap2 = h[10], 0
+                for i in again:
+                    for r, spec in enumerate(h[9][i]):
+                        o = base[i] + r
+                        raw_px = 3 * wh[2 * o] * wh[2 * o + 1] if len(spec) > 12 and spec[12] else 0
+                        cap2 += raw_px or max(8 << 20, 16 * len(streams_of[len(res)][i]))
+                redo = self._transcode_specs([streams_of[len(res)][i] for i in again], [h[9][i] for i in again], cap2)
+                for i, row, row_st in zip(again, redo, self.last_status):
+                    out[i], st[i] = row, row_st
+            res.append(out)
+            sts.append(st)
         self.last_status = sts
         return res
 
@@ -843,7 +953,7 @@ class Engine:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
     def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
-                        stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None) -> List[List[Optional[bytes]]]:
+                        stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
@@ -851,12 +961,13 @@ class Engine:
         every picture, or one entry per batch (each what transcode() takes).  crop / cover likewise: one
         window / box for every picture, or one entry per batch; orient likewise: one value (0..8 or "auto")
         for every picture, or one entry per batch; qscale and sharpen likewise: one int for every picture, or one
-        entry per batch."""
-        if any(v is not None for v in (crop, cover, orient, qscale, sharpen)):
+        entry per batch; format likewise: one name for every picture, or one entry per batch."""
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format)):
             one_orient = isinstance(orient, (str, int, np.integer))
             one_int = lambda v: isinstance(v, (int, np.integer))
             for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover)), ("orient", orient, one_orient),
-                                 ("qscale", qscale, one_int(qscale)), ("sharpen", sharpen, one_int(sharpen))):
+                                 ("qscale", qscale, one_int(qscale)), ("sharpen", sharpen, one_int(sharpen)),
+                                 ("format", format, isinstance(format, str))):
                 if v is not None and not one and len(v) != len(batches):
                     raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
             pick = lambda v, one, bi: v if v is None or one else v[bi]
@@ -866,7 +977,7 @@ class Engine:
                                    pick(fit, _is_pair(fit), bi), pick(stretch, isinstance(stretch, (bool, np.bool_)), bi),
                                    pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi),
                                    pick(orient, one_orient, bi), pick(qscale, one_int(qscale), bi),
-                                   pick(sharpen, one_int(sharpen), bi))
+                                   pick(sharpen, one_int(sharpen), bi), pick(format, isinstance(format, str), bi))
                      for bi, streams in enumerate(batches)]
             res = self._multi_async(batches, rends)
             self.last_status = [[st[0] for st in b] for b in self.last_status]

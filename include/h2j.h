@@ -273,6 +273,57 @@ int64_t h2j_engine_submit_multi5(h2j_engine *e, int n, const uint8_t *const *dat
                                  const int32_t *nrend, const h2j_out_opts5 *opts, uint8_t *out, size_t out_cap,
                                  size_t *out_off, size_t *out_len, int *status);
 
+/* RGB output: a rendition as raw pixels instead of a file (DESIGN.md "RGB output (K3c)").  h2j_out_opts6 is
+ * h2j_out_opts5 with one more reserved word named.
+ * format: H2J_FMT_JPEG (0): the JPEG, as every other call.  H2J_FMT_RGB8 / H2J_FMT_RGB8_PLANAR: the rendition's
+ *   final 8-bit planes -- after orientation, window, scale / fit and sharpen: the planes
+ *   h2j_engine_decode_multi5 shows and K4 would read -- converted to 8-bit RGB on the GPU.  For the planes Y (H x W)
+ *   and Cb, Cr (H/2 x W/2), W and H even, the chroma upsampled with JFIF's centred siting by the 9-3-3-1 triangle
+ *   filter at 16 x precision, all in int32 with one rounding:
+ *     cx = x >> 1, nx = clamp(cx + ((x & 1) ? 1 : -1), 0, W/2 - 1);  cy, ny likewise with y, H/2
+ *     C16(x, y) = 9 C[cy][cx] + 3 C[cy][nx] + 3 C[ny][cx] + C[ny][nx]
+ *     db = Cb16 - 2048, dr = Cr16 - 2048
+ *     R = clip(((Y << 20) + 91881 dr + (1 << 19)) >> 20, 0, 255)
+ *     G = clip(((Y << 20) - 22554 db - 46802 dr + (1 << 19)) >> 20, 0, 255)
+ *     B = clip(((Y << 20) + 116130 db + (1 << 19)) >> 20, 0, 255)                      (arithmetic shifts)
+ *   The matrix is JFIF's (BT.601 full range) whatever the stream's VUI says: the RGB is what a viewer shows for the
+ *   JPEG of the same rendition, without the JPEG loss.  No header.  H2J_FMT_RGB8: interleaved R, G, B, rows of
+ *   exactly 3 W bytes (numpy (H, W, 3)); H2J_FMT_RGB8_PLANAR: an R plane, then G, then B, each W H bytes (numpy
+ *   (3, H, W)).  3 W H bytes either way, at out + out_off[i], out_len[i] of them.
+ * format outside 0..2, a raw format together with qscale (there is no quantiser) or non-zero reserved: that
+ * rendition fails alone with H2J_ERR_OUT_OPTS.  On a kernel library without the stage (h2j_gpu_rgb) a raw
+ * rendition fails alone with H2J_ERR_NO_STAGE.  A raw rendition that does not fit what is left of out_cap gets -50
+ * like a JPEG; when its size alone decides that, the GPU stage does not run for it. */
+#define H2J_FMT_JPEG 0
+#define H2J_FMT_RGB8 1
+#define H2J_FMT_RGB8_PLANAR 2
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts5 */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window of the oriented picture */
+    int32_t orient;                                   /* 0..8, or H2J_ORIENT_AUTO */
+    int32_t qscale;                                   /* 0, or 2..31 (0 with a raw format) */
+    int32_t sharpen;                                  /* 0..64, in 1/16 */
+    int32_t format;                                   /* H2J_FMT_* */
+    int32_t reserved[3];                              /* must be 0 */
+} h2j_out_opts6;                                      /* 64 bytes */
+
+/* h2j_crop_window5 with h2j_out_opts6: the same window, size and orientation, and the format checks.
+ * Returns 0, or H2J_ERR_OUT_OPTS (nothing is written). */
+int h2j_crop_window6(int w, int h, const h2j_out_opts6 *o, int sei_orient, int32_t *win, int *ow, int *oh, int *orient);
+
+/* h2j_engine_transcode_multi5 / h2j_engine_submit_multi5 with h2j_out_opts6; an h2j_out_opts5 item is the
+ * h2j_out_opts6 item with format 0 (the multi5 calls keep rejecting non-zero reserved words).  out_wh (may be NULL):
+ * two entries per rendition, the output's W, H; written (else 0, 0) for every rendition of a parsed item whose
+ * options resolve, JPEG renditions and those that got -50 too, so a caller can size a retry exactly.  A raw
+ * rendition with the (orientation, window, output, sharpen) of a JPEG rendition of the same item reads that
+ * rendition's planes: the scale stage runs once for both. */
+int h2j_engine_transcode_multi6(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts6 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status, int32_t *out_wh);
+int64_t h2j_engine_submit_multi6(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                 const int32_t *nrend, const h2j_out_opts6 *opts, uint8_t *out, size_t out_cap,
+                                 size_t *out_off, size_t *out_len, int *status, int32_t *out_wh);
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -324,7 +375,8 @@ int h2j_engine_decode_multi5(h2j_engine *e, const uint8_t *data, size_t size, in
  * [12] K0 prep  [13] chunks  [14] record packing (host)  [15] parse (host, wall, first to last
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
  * h2j.py  [22] K3o / K3s / K3r / K3p / K3u orientation, scaled- and exact-size-output and finishing stage (GPU)  [23] renditions: JPEG outputs
- * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran. */
+ * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran
+ * [25] raw bytes: the bytes of the raw (RGB) renditions delivered ([22] includes K3c, the RGB stage). */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).
@@ -366,6 +418,10 @@ int h2j_h265_to_jpeg_mem_multi4(const uint8_t *data, size_t size, int nrend, con
 /* the same with h2j_out_opts5 (finishing): concurrent callers with different finishing options still share GPU batches */
 int h2j_h265_to_jpeg_mem_multi5(const uint8_t *data, size_t size, int nrend, const h2j_out_opts5 *opts, uint8_t **jpeg,
                                 size_t *jpeg_len, int *status);
+/* the same with h2j_out_opts6 (RGB output): jpeg[r] of a raw rendition holds its jpeg_len[r] = 3 W H pixel bytes;
+ * out_wh (may be NULL) as in h2j_engine_transcode_multi6 */
+int h2j_h265_to_jpeg_mem_multi6(const uint8_t *data, size_t size, int nrend, const h2j_out_opts6 *opts, uint8_t **jpeg,
+                                size_t *jpeg_len, int *status, int32_t *out_wh);
 void h2j_free(void *p);
 
 /* Library self-description (version, arch, build). */

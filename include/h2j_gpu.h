@@ -105,6 +105,9 @@ constexpr int h2j_k3u_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) 
 constexpr int h2j_k3u_tiles(int jpeg_w, int jpeg_h) {
     return h2j_k3u_plane_tiles(jpeg_w, jpeg_h) + 2 * h2j_k3u_plane_tiles(jpeg_w / 2, jpeg_h / 2);
 }
+/* K3c (RGB output) workgroups (256 lanes: 64 lanes of 4 adjacent pixels x 4 lane rows; lane row j makes the output
+ * rows 2 j - 1 and 2 j, which share the chroma rows j - 1 and j: h / 2 + 1 lane rows) of one w x h output */
+constexpr int h2j_k3c_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * (((h >> 1) + 1 + 3) >> 2); }
 /* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
  * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
@@ -233,6 +236,17 @@ int h2j_gpu_orient(const h2j_gpu_batch *b, const h2j_orient *map, const int32_t 
 #define H2J_FINISH_CLASSES 3
 int h2j_gpu_finish(const h2j_gpu_batch *b, const h2j_finish *map, const int32_t *first, const int32_t *count,
                    const int32_t *tiles, void *stream);
+/* K3c: the raw (RGB) outputs (h2j_rgb, a device array), grouped by source class as K3u's (0: the 8-bit planes K3s /
+ * K3r / K3p / K3u wrote, h2j_rgb.wide; 1: another 8-bit source; 2: a 16-bit source): source planes -> w x h 8-bit
+ * RGB pixels at h2j_rgb.dst_base + dst_off, interleaved or planar, tightly packed (DESIGN.md "RGB output (K3c)":
+ * JFIF's matrix, the chroma through the 9-3-3-1 triangle filter).  first / count / tiles: per class (host arrays
+ * of H2J_RGB_CLASSES), tiles the most workgroups one output of the class needs (h2j_k3c_tiles); one launch per
+ * class present.  Runs after h2j_gpu_finish, whose outputs it may read, and before K4; out of place.  A kernel
+ * library older than the stage lacks the symbol: the host library resolves it when it loads and fails raw
+ * renditions alone (H2J_ERR_NO_STAGE) */
+#define H2J_RGB_CLASSES 3
+int h2j_gpu_rgb(const h2j_gpu_batch *b, const h2j_rgb *map, const int32_t *first, const int32_t *count,
+                const int32_t *tiles, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat
  * (variance, rate control, FDCT + quantiser + zigzag, symbol histograms) */

@@ -190,6 +190,25 @@ typedef struct {
                                        picture's */
 } h2j_finish;
 
+/* One raw (RGB) output of a batch (DESIGN.md "RGB output (K3c)"): K3c reads the planes the output's JPEG source view
+ * shows K4 -- the 8-bit planes K3s / K3r / K3p or K3u wrote (16-byte row groups), or an unscaled frame, window or
+ * oriented source in the frame's sample type -- and writes w x h 8-bit RGB pixels, tightly packed (no row or plane
+ * padding: 3 w h bytes), at dst_base + dst_off.  The record describes its source itself (no h2j_frame is read). */
+typedef struct {
+    int32_t w, h;                   /* luma size of the output (both even) */
+    int32_t layout;                 /* 1: interleaved R, G, B (rows of 3 w bytes); 2: an R, a G and a B plane of w h bytes
+                                       each (H2J_FMT_RGB8, H2J_FMT_RGB8_PLANAR of include/h2j.h) */
+    int32_t bit_depth, bit_depth_c; /* of the source samples (8: uint8_t planes, above: uint16_t) */
+    int32_t crop_x, crop_y;         /* the source's first luma sample inside its planes */
+    int32_t wide;                   /* 1: an 8-bit source with 16-byte row groups and no crop (the planes K3s / K3r /
+                                       K3p / K3u wrote): aligned dword loads */
+    uint64_t src;                   /* source planes (arena offset, bytes) */
+    int32_t src_stride[3];          /* elements per row */
+    int32_t src_off[3];             /* element offset of each plane inside src */
+    uint64_t dst_base;              /* 0: the batch's arena; else a device address (caller-owned memory: not used yet) */
+    uint64_t dst_off;               /* byte offset of the pixels from that base (the arena: 256-byte aligned) */
+} h2j_rgb;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;
