@@ -406,81 +406,47 @@ void build_scale_classes(ChunkPlan& p) {
     }
 }
 
-// K3o map: the oriented sources by class (sample type x transposing), one launch per class present, its grid
-// as wide as the class's largest picture needs
-void build_orient_classes(ChunkPlan& p) {
-    for (int cls = 0; cls < H2J_ORIENT_CLASSES && !p.orients.empty(); cls++) {
-        p.orient_first[cls] = static_cast<int32_t>(p.orientmap.size());
-        for (const h2j_orient& rec : p.orients) {
-            const h2j_frame& f = p.frames[rec.frame];
-            const int pel = f.bit_depth > 8 ? 2 : 1;
-            const bool tr = rec.orient >= 5;
-            if (2 * (pel - 1) + (tr ? 1 : 0) != cls) continue;
-            p.orientmap.push_back(rec);
-            p.orient_count[cls]++;
-            p.orient_tiles[cls] = std::max(p.orient_tiles[cls], h2j_k3o_tiles(tr ? f.out_h : f.out_w, tr ? f.out_w : f.out_h, pel, tr));
-        }
+// the source half of a K3u or K3c record (the fields have the same names in both): the planes K3u / K3c read, as
+// the view `src` shows them; wide: the 8-bit planes a scale or finishing kernel wrote (aligned dword loads)
+template <typename Rec>
+void fill_source(Rec& rec, const h2j_frame& src, bool wide) {
+    rec.bit_depth = src.bit_depth;
+    rec.bit_depth_c = src.bit_depth_c;
+    rec.crop_x = src.crop_x;
+    rec.crop_y = src.crop_y;
+    rec.wide = wide ? 1 : 0;
+    rec.src = src.pic2;
+    for (int c = 0; c < 3; c++) {
+        rec.src_stride[c] = src.pic_stride[c];
+        rec.src_off[c] = src.pic_off[c];
     }
 }
+// the class of a K3u or K3c record: 0: the 8-bit planes K3s / K3r / K3p (/ K3u) wrote; 1: another 8-bit source; 2: a
+// 16-bit source
+template <typename Rec>
+int source_class(const Rec& rec) { return rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1; }
 
-// K3u map: the sharpened outputs with their sources (what each view is without its sharpening), by source class
-// (0: the 8-bit planes K3s / K3r / K3p wrote; 1: another 8-bit source; 2: a 16-bit source), one launch per class
-// present, its grid as wide as the class's largest output needs
-void build_finish_classes(ChunkPlan& p) {
-    for (int v = 0; v < p.nv; v++) {
-        if (p.vfin[v] < 0) continue;
-        h2j_finish& rec = p.fins[p.vfin[v]];
-        const h2j_frame src = p.base_view(v);
-        rec.bit_depth = src.bit_depth;
-        rec.bit_depth_c = src.bit_depth_c;
-        rec.crop_x = src.crop_x;
-        rec.crop_y = src.crop_y;
-        rec.wide = p.scaled[v].scale_log2 != 0 ? 1 : 0;
-        rec.src = src.pic2;
-        for (int c = 0; c < 3; c++) {
-            rec.src_stride[c] = src.pic_stride[c];
-            rec.src_off[c] = src.pic_off[c];
-        }
-    }
-    for (int cls = 0; cls < H2J_FINISH_CLASSES && !p.fins.empty(); cls++) {
-        p.fin_first[cls] = static_cast<int32_t>(p.finmap.size());
-        for (const h2j_finish& rec : p.fins) {
-            if ((rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1) != cls) continue;
-            p.finmap.push_back(rec);
-            p.fin_count[cls]++;
-            p.fin_tiles[cls] = std::max(p.fin_tiles[cls], h2j_k3u_tiles(rec.w, rec.h));
-        }
-    }
-}
-
-// K3c map: the raw outputs with their sources (what view() shows K4), by source class as K3u's (0: the 8-bit planes
-// K3s / K3r / K3p / K3u wrote; 1: another 8-bit source; 2: a 16-bit source), one launch per class present, its grid
-// as wide as the class's largest output needs
-void build_rgb_classes(ChunkPlan& p) {
+// The late stages' maps (ChunkPlan::StageMap), each grouped by class, one launch per class present, its grid as wide
+// as the class's largest picture needs
+void build_late_stage_maps(ChunkPlan& p) {
+    // K3o: the oriented sources, by sample type x transposing
+    p.orientmap.group(p.orients,
+                      [&](const h2j_orient& rec) { return 2 * (p.frames[rec.frame].bit_depth > 8 ? 1 : 0) + (rec.orient >= 5 ? 1 : 0); },
+                      [&](const h2j_orient& rec) {
+                          const h2j_frame& f = p.frames[rec.frame];
+                          const bool tr = rec.orient >= 5;
+                          return h2j_k3o_tiles(tr ? f.out_h : f.out_w, tr ? f.out_w : f.out_h, f.bit_depth > 8 ? 2 : 1, tr);
+                      });
+    // K3u: the sharpened outputs with their sources (what each view is without its sharpening)
+    for (int v = 0; v < p.nv; v++)
+        if (p.vfin[v] >= 0) fill_source(p.fins[p.vfin[v]], p.base_view(v), p.scaled[v].scale_log2 != 0);
+    p.finmap.group(p.fins, source_class<h2j_finish>, [](const h2j_finish& rec) { return h2j_k3u_tiles(rec.w, rec.h); });
+    // K3c: the raw outputs with their sources (what view() shows K4)
     for (size_t i = 0; i < p.rgbs.size(); i++) {
-        h2j_rgb& rec = p.rgbs[i];
         const int v = p.rgbview[i];
-        const h2j_frame src = p.view(v);
-        rec.bit_depth = src.bit_depth;
-        rec.bit_depth_c = src.bit_depth_c;
-        rec.crop_x = src.crop_x;
-        rec.crop_y = src.crop_y;
-        rec.wide = (p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0) ? 1 : 0;
-        rec.src = src.pic2;
-        for (int c = 0; c < 3; c++) {
-            rec.src_stride[c] = src.pic_stride[c];
-            rec.src_off[c] = src.pic_off[c];
-        }
+        fill_source(p.rgbs[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0);
     }
-    for (int cls = 0; cls < H2J_RGB_CLASSES && !p.rgbs.empty(); cls++) {
-        p.rgb_first[cls] = static_cast<int32_t>(p.rgbmap.size());
-        for (const h2j_rgb& rec : p.rgbs) {
-            if ((rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1) != cls) continue;
-            p.rgbmap.push_back(rec);
-            p.rgb_count[cls]++;
-            p.rgb_tiles[cls] = std::max(p.rgb_tiles[cls], h2j_k3c_tiles(rec.w, rec.h));
-        }
-    }
+    p.rgbmap.group(p.rgbs, source_class<h2j_rgb>, [](const h2j_rgb& rec) { return h2j_k3c_tiles(rec.w, rec.h); });
 }
 
 // the maps' places in the staging buffer, behind the records; with scaled pictures or several
@@ -500,14 +466,12 @@ void layout_maps(ChunkPlan& p) {
     }
     p.at.pyr = c.off;
     if (!p.pyrmap.empty()) c.take(p.pyrmap.size() * sizeof(h2j_pyramid) + 16);
-    p.at.orient = c.off;  // only in chunks with oriented sources: every offset above is what it was
-    if (!p.orientmap.empty()) c.take(p.orientmap.size() * sizeof(h2j_orient) + 16);
-    p.at.finish = c.off;  // only in chunks with sharpened outputs, and
-    if (!p.finmap.empty()) c.take(p.finmap.size() * sizeof(h2j_finish) + 16);
+    // the late stages' maps, each only in chunks that have the stage: every offset above is what it was
+    p.orientmap.at = c.take(p.orientmap.staging_bytes());
+    p.finmap.at = c.take(p.finmap.staging_bytes());
     p.at.qforce = c.off;  // only in chunks with a forced quantiser scale: one int32 a view
     if (p.qforced) c.take(static_cast<size_t>(p.nv) * 4 + 16);
-    p.at.rgb = c.off;  // only in chunks with raw outputs
-    if (!p.rgbmap.empty()) c.take(p.rgbmap.size() * sizeof(h2j_rgb) + 16);
+    p.rgbmap.at = c.take(p.rgbmap.staging_bytes());
     p.at.jcompact = c.off;  // only in chunks with views that get no JPEG: the views K4 / K5 run on
     if (p.compact()) c.take(static_cast<size_t>(p.njpeg) * sizeof(h2j_frame));
     p.at.bytes = c.off;
@@ -614,38 +578,32 @@ h2j_frame ChunkPlan::wframe(int j) const {
     return f;
 }
 
+inline void clear_all() {}
+template <typename V, typename... Vs>
+void clear_all(V& v, Vs&... vs) {
+    v.clear();
+    clear_all(vs...);
+}
+
+void ChunkPlan::reset(int nframes) {
+    nf = nframes;
+    frames.resize(static_cast<size_t>(nf));
+    vfirst.assign(static_cast<size_t>(nf) + 1, 0);
+    fstat.assign(static_cast<size_t>(nf), 0);
+    clear_all(k1map, k1map8, k1all, k1hevc, saomap, scaled, scalemap, pyrmap, vsrc, wins, rends, jviews);
+    clear_all(orients, orientmap, vqscale, vsharpen, fins, finmap, rgbs, rgbview, rgbmap, vjpeg);
+    qforced = false;
+    px = 0;
+    std::memset(&desc, 0, sizeof(desc));
+}
+
 void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live, ChunkPlan& p) {
-    p.nf = static_cast<int>(live.size());
-    p.frames.resize(static_cast<size_t>(p.nf));
-    p.vfirst.assign(static_cast<size_t>(p.nf) + 1, 0);
-    for (auto* m : {&p.k1map, &p.k1map8, &p.k1all, &p.k1hevc, &p.saomap}) m->clear();
-    p.scaled.clear();
-    p.vsrc.clear();
-    p.wins.clear();
-    p.orients.clear();
-    p.orientmap.clear();
-    for (int cls = 0; cls < H2J_ORIENT_CLASSES; cls++) p.orient_first[cls] = p.orient_count[cls] = p.orient_tiles[cls] = 0;
-    for (auto* m : {&p.fins, &p.finmap}) m->clear();
-    p.vqscale.clear();
-    p.vsharpen.clear();
-    for (auto* m : {&p.rgbs, &p.rgbmap}) m->clear();
-    p.rgbview.clear();
-    p.vjpeg.clear();
-    for (int cls = 0; cls < H2J_RGB_CLASSES; cls++) p.rgb_first[cls] = p.rgb_count[cls] = p.rgb_tiles[cls] = 0;
-    p.qforced = false;
-    for (int cls = 0; cls < H2J_FINISH_CLASSES; cls++) p.fin_first[cls] = p.fin_count[cls] = p.fin_tiles[cls] = 0;
-    p.fstat.assign(static_cast<size_t>(p.nf), 0);
-    p.rends.clear();
-    p.scalemap.clear();
-    p.pyrmap.clear();
-    p.px = 0;
-    std::memset(&p.desc, 0, sizeof(p.desc));
+    p.reset(static_cast<int>(live.size()));
     number_frames_and_views(jobs, live, p);
     // scaled pictures present, or several renditions of a frame: a views array is uploaded
     p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; }) ||
               std::any_of(p.vsharpen.begin(), p.vsharpen.end(), [](int a) { return a != 0; });  // ... or a sharpened view
     p.njpeg = static_cast<int>(std::count(p.vjpeg.begin(), p.vjpeg.end(), 1));
-    p.jviews.clear();
     for (int v = 0; v < p.nv && p.compact(); v++)
         if (p.vjpeg[v]) p.jviews.push_back(v);
     p.vjcoef.resize(static_cast<size_t>(p.nv));
@@ -654,9 +612,7 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     build_k1_maps(p);
     build_sao_classes(p);
     build_scale_classes(p);
-    build_orient_classes(p);
-    build_finish_classes(p);
-    build_rgb_classes(p);
+    build_late_stage_maps(p);
     layout_maps(p);
     fill_descriptor(p);
 }

@@ -2,6 +2,7 @@
 // touches a buffer -- frames and views, the arena layout, the workgroup maps, the staging layout and the
 // scalar fields of the batch descriptor.  Pure host arithmetic on the job records: no GPU call.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -18,6 +19,37 @@ constexpr int kK1BandRows = 68;
 constexpr size_t kSegBytesPerBlock = 272;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The map of a late stage (K3o, K3u, K3c; include/h2j_gpu.h h2j_gpu_orient, h2j_gpu_finish, h2j_gpu_rgb): the stage's
+// records grouped by class, uploaded behind the other maps, with each class's first record, count and the most
+// workgroups one record of the class needs -- one launch per class present.  A chunk without the stage has an empty
+// map, uploads nothing for it and does not launch it
+template <typename Rec, int NCLS>
+struct StageMap {
+    std::vector<Rec> map;
+    int32_t first[NCLS] = {0}, count[NCLS] = {0}, tiles[NCLS] = {0};
+    size_t at = 0;  // the map's byte offset in the staging buffer
+    void clear() {
+        map.clear();
+        for (int cls = 0; cls < NCLS; cls++) first[cls] = count[cls] = tiles[cls] = 0;
+    }
+    bool empty() const { return map.empty(); }
+    size_t bytes() const { return map.size() * sizeof(Rec); }
+    size_t staging_bytes() const { return empty() ? 0 : bytes() + 16; }  // nothing: the offsets behind it are what they were
+    // the records in class order, their own order inside a class
+    template <typename ClassOf, typename TilesOf>
+    void group(const std::vector<Rec>& records, ClassOf class_of, TilesOf tiles_of) {
+        for (int cls = 0; cls < NCLS && !records.empty(); cls++) {
+            first[cls] = static_cast<int32_t>(map.size());
+            for (const Rec& rec : records) {
+                if (class_of(rec) != cls) continue;
+                map.push_back(rec);
+                count[cls]++;
+                tiles[cls] = std::max<int32_t>(tiles[cls], tiles_of(rec));
+            }
+        }
+    }
+};
 
 struct ChunkPlan {
     // Frames and views: nf frames (decoded pictures) and nv >= nf JPEG source views, frame-major.  A view
@@ -60,9 +92,8 @@ struct ChunkPlan {
     // of it (the whole picture is the window 0, 0, W, H): its frame copy has pic == pic2 == opic, no
     // conformance crop and the oriented strides, so K3s, K3r, K3p and K4 read it with the code they have.
     // A chunk without oriented outputs has none of this and uploads what it always did
-    std::vector<h2j_orient> orients;    // the chunk's oriented sources, frame-major
-    std::vector<h2j_orient> orientmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_orient), uploaded
-    int32_t orient_first[H2J_ORIENT_CLASSES] = {0}, orient_count[H2J_ORIENT_CLASSES] = {0}, orient_tiles[H2J_ORIENT_CLASSES] = {0};
+    std::vector<h2j_orient> orients;                      // the chunk's oriented sources, frame-major
+    StageMap<h2j_orient, H2J_ORIENT_CLASSES> orientmap;  // the same grouped by class (sample type x transposing)
 
     // Finishing (K3u, forced qscale): a view is (frame, window, resolved output, qscale, sharpen).  Views that differ
     // only in qscale or sharpen share nothing: each has its scaled planes and runs the scale stage for itself (of
@@ -75,8 +106,7 @@ struct ChunkPlan {
     std::vector<int> vsharpen;       // per view: the unsharp mask's strength, 0: none
     std::vector<int> vfin;           // per view: -1, or its record in fins
     std::vector<h2j_finish> fins;    // the chunk's sharpened outputs, view-major
-    std::vector<h2j_finish> finmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_finish), uploaded
-    int32_t fin_first[H2J_FINISH_CLASSES] = {0}, fin_count[H2J_FINISH_CLASSES] = {0}, fin_tiles[H2J_FINISH_CLASSES] = {0};
+    StageMap<h2j_finish, H2J_FINISH_CLASSES> finmap;  // the same grouped by source class
     bool qforced = false;            // a view of the chunk forces its quantiser scale
     h2j_frame base_view(int v) const;  // view v without its sharpening: what K3u reads
 
@@ -88,8 +118,7 @@ struct ChunkPlan {
     // beside the JPEG payloads.  A chunk without raw outputs has none of this and uploads what it always did
     std::vector<h2j_rgb> rgbs;    // the chunk's raw outputs, view-major
     std::vector<int> rgbview;     // per raw output: its view
-    std::vector<h2j_rgb> rgbmap;  // the same grouped by class (include/h2j_gpu.h h2j_gpu_rgb), uploaded
-    int32_t rgb_first[H2J_RGB_CLASSES] = {0}, rgb_count[H2J_RGB_CLASSES] = {0}, rgb_tiles[H2J_RGB_CLASSES] = {0};
+    StageMap<h2j_rgb, H2J_RGB_CLASSES> rgbmap;  // the same grouped by source class
     size_t rgb_base = 0, rgb_bytes = 0;  // the region: arena offset, bytes (whole 256-byte groups)
     std::vector<char> vjpeg;      // per view: a JPEG rendition shows it (else raw ones only: its JPEG is never assembled)
     int njpeg = 0;                // such views; 0: a chunk of raw renditions only, which runs no K4 / K5
@@ -115,8 +144,8 @@ struct ChunkPlan {
     // staging layout: byte offset of each array in the one buffer the chunk uploads
     struct Staging {
         size_t frames = 0, tus = 0, coefs = 0, ctbs = 0, slices = 0, sl = 0, k1map = 0, k1all = 0, sao = 0, k1map8 = 0,
-               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, orient = 0, finish = 0, qforce = 0, rgb = 0, jcompact = 0, bytes = 0;
-    } at;
+               k1hevc = 0, jframes = 0, scale = 0, pyr = 0, qforce = 0, jcompact = 0, bytes = 0;
+    } at;  // (the late stages' maps: StageMap::at)
 
     // the descriptor's scalar fields (counts, maxima, codec / sample-type masks, classes); its pointers,
     // jpeg_dense and seg_cap are the engine's to fill once it has the buffers
@@ -124,6 +153,9 @@ struct ChunkPlan {
 
     // the JPEG source view of view v: what K4 (variance, FDCT) and K5 read as "the picture"
     h2j_frame view(int v) const;
+
+    // an empty plan of nf frames; the vectors keep their capacity from chunk to chunk
+    void reset(int nframes);
 };
 
 // Plan the chunk of jobs[live[0..]] (parsed jobs, each with at least one valid output: every frame has a view) into p; p's vectors are

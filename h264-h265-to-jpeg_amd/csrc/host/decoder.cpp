@@ -24,7 +24,7 @@
 
 #include "IDecoder.h"
 #include "h2j.h"
-#include "job.h"
+#include "out_opts.h"
 
 void LOG(const char* format, ...) {
     char log[1024] = {0};
@@ -289,16 +289,6 @@ extern "C" int h2j_h265_to_jpeg_mem(const uint8_t* data, size_t size, uint8_t** 
     return h2j_h265_to_jpeg_mem_scaled(data, size, 0, 0, jpeg, jpeg_len);
 }
 
-static h2j_out_opts6 opts6_of(const h2j_out_opts3& o) {
-    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, 0, 0, 0, 0,
-                         {o.reserved[0], o.reserved[1], o.reserved[2]}};
-}
-static h2j_out_opts6 opts6_of(const h2j_out_opts2& o) {
-    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, 0, 0, 0, 0, 0, 0, 0, 0, {o.reserved[0], o.reserved[1], o.reserved[2]}};
-}
-static h2j_out_opts6 opts6_of(const h2j_out_opts4& o) { return h2j::widen_opts5(h2j::widen_opts4(o)); }
-static h2j_out_opts6 opts6_of(const h2j_out_opts5& o) { return h2j::widen_opts5(o); }
-
 static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& opts, uint8_t** jpeg, size_t* jpeg_len) {
     if (!jpeg || !jpeg_len) return -1;
     *jpeg = nullptr;
@@ -307,7 +297,7 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts[0] = opts6_of(opts);
+    req.opts[0] = h2j::to_opts6(opts);
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -329,42 +319,6 @@ extern "C" int h2j_h265_to_jpeg_mem_scaled(const uint8_t* data, size_t size, int
 extern "C" int h2j_h265_to_jpeg_mem_fit(const uint8_t* data, size_t size, int fit_w, int fit_h, int flags, uint8_t** jpeg,
                                         size_t* jpeg_len) {
     return to_jpeg_mem(data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, jpeg, jpeg_len);
-}
-
-extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, uint8_t** jpeg,
-                                          size_t* jpeg_len, int* status) {
-    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (!opts) return -1;
-    std::vector<h2j_out_opts6> o6;
-    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
-}
-
-extern "C" int h2j_h265_to_jpeg_mem_multi3(const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, uint8_t** jpeg,
-                                           size_t* jpeg_len, int* status) {
-    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (!opts) return -1;
-    std::vector<h2j_out_opts6> o6;
-    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
-}
-
-extern "C" int h2j_h265_to_jpeg_mem_multi4(const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, uint8_t** jpeg,
-                                           size_t* jpeg_len, int* status) {
-    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (!opts) return -1;
-    std::vector<h2j_out_opts6> o6;
-    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
-}
-
-extern "C" int h2j_h265_to_jpeg_mem_multi5(const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, uint8_t** jpeg,
-                                           size_t* jpeg_len, int* status) {
-    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
-    if (!opts) return -1;
-    std::vector<h2j_out_opts6> o6;
-    for (int r = 0; r < nrend; r++) o6.push_back(opts6_of(opts[r]));
-    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, o6.data(), jpeg, jpeg_len, status, nullptr);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi6(const uint8_t* data, size_t size, int nrend, const h2j_out_opts6* opts, uint8_t** jpeg,
@@ -401,6 +355,31 @@ extern "C" int h2j_h265_to_jpeg_mem_multi6(const uint8_t* data, size_t size, int
         jpeg_len[r] = req.jpegs[r].size();
     }
     return 0;
+}
+
+// the multi calls on items of any older option type T
+template <typename T>
+static int to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const T* opts, uint8_t** jpeg, size_t* jpeg_len, int* status) {
+    if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
+    if (!opts) return -1;
+    return h2j_h265_to_jpeg_mem_multi6(data, size, nrend, h2j::to_opts6(nrend, opts).data(), jpeg, jpeg_len, status, nullptr);
+}
+
+extern "C" int h2j_h265_to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const h2j_out_opts2* opts, uint8_t** jpeg,
+                                          size_t* jpeg_len, int* status) {
+    return to_jpeg_mem_multi(data, size, nrend, opts, jpeg, jpeg_len, status);
+}
+extern "C" int h2j_h265_to_jpeg_mem_multi3(const uint8_t* data, size_t size, int nrend, const h2j_out_opts3* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status) {
+    return to_jpeg_mem_multi(data, size, nrend, opts, jpeg, jpeg_len, status);
+}
+extern "C" int h2j_h265_to_jpeg_mem_multi4(const uint8_t* data, size_t size, int nrend, const h2j_out_opts4* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status) {
+    return to_jpeg_mem_multi(data, size, nrend, opts, jpeg, jpeg_len, status);
+}
+extern "C" int h2j_h265_to_jpeg_mem_multi5(const uint8_t* data, size_t size, int nrend, const h2j_out_opts5* opts, uint8_t** jpeg,
+                                           size_t* jpeg_len, int* status) {
+    return to_jpeg_mem_multi(data, size, nrend, opts, jpeg, jpeg_len, status);
 }
 
 extern "C" void h2j_free(void* p) { free(p); }

@@ -76,21 +76,6 @@ struct FrameJob {
     }
 };
 
-// h2j_out_opts5 is the engine's one option type.  An h2j_out_opts4 item is the h2j_out_opts5 item with qscale and
-// sharpen 0; the two words they took over were reserved there and still must be 0: a non-zero one stays a
-// non-zero reserved word
-inline h2j_out_opts5 widen_opts4(const h2j_out_opts4& o) {
-    return h2j_out_opts5{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient, 0, 0,
-                         {o.reserved[0] | o.reserved[1] | o.reserved[2], o.reserved[3], o.reserved[4], o.reserved[5]}};
-}
-
-// ... and h2j_out_opts6 took one more word (format) from h2j_out_opts5, in the same way: the engine's one option type
-// is now h2j_out_opts6, and an h2j_out_opts5 item is the one with format 0
-inline h2j_out_opts6 widen_opts5(const h2j_out_opts5& o) {
-    return h2j_out_opts6{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
-                         o.qscale, o.sharpen, 0, {o.reserved[0] | o.reserved[1], o.reserved[2], o.reserved[3]}};
-}
-
 // Offsets of the scaling-factor tables inside FrameJob::sl
 enum { H2J_SL_S0 = 0, H2J_SL_S1 = 48, H2J_SL_S2 = 240, H2J_SL_S3 = 1008, H2J_SL_BYTES = 2032 };
 // H.264 weight-scale tables inside FrameJob::sl (raster order): 4x4 intra Y/Cb/Cr, 8x8 intra Y

@@ -1,7 +1,8 @@
 """The orientation cases of test_orient_handover.py: what the host engine hands to the GPU library when
 renditions carry an orientation, in the way handover_cases.py does it (same stand-in, same transcript, a
 fresh Engine per call).  The stand-in has no h2j_gpu_orient: it is the older kernel library of the
-H2J_ERR_NO_STAGE rule.  Run as `python orient_handover_cases.py <case>` with H2J_LIB_DIR naming the
+H2J_ERR_NO_STAGE rule (test_handover_recorded.py also runs every case, case d for its oriented plans, against
+tests/fake_gpu/fake_gpu_orient.cpp, which has the stage).  Run as `python orient_handover_cases.py <case>` with H2J_LIB_DIR naming the
 stand-in's directory.
 """
 import os
@@ -85,7 +86,28 @@ def case_c():
     result(status=e.last_status, sof=[[sof_size(j) for j in item] for item in out])
 
 
-CASES = {"a": case_a, "b": case_b, "c": case_c}
+# case d: real oriented plans (only a stand-in with the stage shows them; the one without fails these renditions alone).
+# Orientations 3, 6 and 7, the last two transposing, on an 8-bit HEVC, a 10-bit HEVC and an H.264 picture
+ITEMS_D = [
+    # two renditions with one orientation share one oriented source; an oriented window at another orientation
+    (P12, [{"orient": 6}, {"orient": 6, "scale": 1}, {"orient": 3, "crop": (2, 2, 60, 30)}, 0]),
+    # two K3s levels on an oriented source: a pyramid; a rendition that is oriented, sharpened and raw: K3o, K3u, K3c
+    (P04, [{"orient": 7, "scale": 1}, {"orient": 7, "scale": 2}, {"orient": 3, "scale": 1, "sharpen": 16, "format": "rgb"}]),
+    (A11, [{"orient": 3}, 1, {"orient": 6, "crop": (16, 16, 32, 32), "scale": 1}]),
+]
+
+
+def case_d():
+    import numpy as np
+    e = fresh()
+    say("== oriented plans")
+    out = e.transcode_multi([stream(i) for i, _ in ITEMS_D], [r for _, r in ITEMS_D])
+    result(status=e.last_status, sof=[[["px"] + list(j.shape) if isinstance(j, np.ndarray) else sof_size(j) for j in item] for item in out],
+           errors=[e.frame_error(o) for o in range(sum(len(r) for _, r in ITEMS_D))],
+           renditions=e.stats()["renditions"], parsed=e.stats()["parsed"], frames=e.stats()["frames"])
+
+
+CASES = {"a": case_a, "b": case_b, "c": case_c, "d": case_d}
 ENV = {}
 
 if __name__ == "__main__":
