@@ -1,47 +1,57 @@
 #include "bitstream.h"
 
+#include <cstring>
+
 namespace h2j {
 
+// Both scans below look for a three-byte pattern that ends in a rare byte (01 / 03: one byte in 256 of
+// entropy-coded data), so they search for that byte with memchr (the C library's vector scan) and look
+// at the two bytes before a hit, where a byte-wise loop kept a zero count for every byte.
 void split_annexb(const uint8_t* d, size_t n, std::vector<Nal>& out) {
     out.clear();
-    size_t i = 0;
     long start = -1;
-    while (i + 2 < n) {
-        // fast skip: a start code needs d[i+2] <= 1
-        if (d[i + 2] > 1) {
-            i += 3;
-            continue;
-        }
-        if (d[i] == 0 && d[i + 1] == 0 && d[i + 2] == 1) {
-            if (start >= 0) {
-                size_t e = i;
-                while (e > static_cast<size_t>(start) && d[e - 1] == 0) e--;
-                out.push_back(Nal{d + start, e - start});
-            }
-            i += 3;
-            start = static_cast<long>(i);
-            continue;
-        }
-        i++;
-    }
-    if (start >= 0 && static_cast<size_t>(start) < n) {
-        size_t e = n;
+    auto close = [&](size_t e) {
         while (e > static_cast<size_t>(start) && d[e - 1] == 0) e--;
-        out.push_back(Nal{d + start, e - start});
+        out.push_back(Nal{d + start, e - static_cast<size_t>(start)});
+    };
+    // i: the first byte a start code may begin at (start codes do not overlap: after one, the
+    // search goes on behind its 01)
+    size_t i = 0;
+    while (i + 2 < n) {
+        const uint8_t* one = static_cast<const uint8_t*>(std::memchr(d + i + 2, 1, n - (i + 2)));
+        if (!one) break;
+        const size_t j = static_cast<size_t>(one - d);  // j - 2 >= i
+        if (d[j - 1] == 0 && d[j - 2] == 0) {
+            if (start >= 0) close(j - 2);
+            i = j + 1;
+            start = static_cast<long>(i);
+        } else {
+            i = j - 1;  // this 01 ends no start code; the next may begin at j - 1 at the earliest
+        }
     }
+    if (start >= 0 && static_cast<size_t>(start) < n) close(n);
 }
 
 size_t unescape_rbsp(const uint8_t* src, size_t n, uint8_t* dst) {
-    size_t o = 0;
-    int zeros = 0;
-    for (size_t i = 0; i < n; i++) {
-        uint8_t b = src[i];
-        if (zeros >= 2 && b == 3) {
-            zeros = 0;
-            continue;
+    // an emulation-prevention byte is a 03 after two zero bytes that lie behind the previous
+    // removed one (the zero count restarts there): the stretches between them are copied whole
+    size_t o = 0, seg = 0, from = 2;
+    while (from < n) {
+        const uint8_t* three = static_cast<const uint8_t*>(std::memchr(src + from, 3, n - from));
+        if (!three) break;
+        const size_t j = static_cast<size_t>(three - src);  // j - 2 >= seg
+        if (src[j - 1] == 0 && src[j - 2] == 0) {
+            std::memcpy(dst + o, src + seg, j - seg);
+            o += j - seg;
+            seg = j + 1;
+            from = seg + 2;
+        } else {
+            from = j + 1;
         }
-        dst[o++] = b;
-        zeros = (b == 0) ? zeros + 1 : 0;
+    }
+    if (seg < n) {
+        std::memcpy(dst + o, src + seg, n - seg);
+        o += n - seg;
     }
     return o;
 }

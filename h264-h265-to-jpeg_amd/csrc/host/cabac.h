@@ -18,9 +18,56 @@ struct ResidualStats {
 };
 extern thread_local ResidualStats g_rstat;
 #define H2J_STAT(f, n) (g_rstat.f += (n))
+// Data-dependent branches of the HEVC slice-data path as named sites (parse_bench -B).  Each site
+// counts its executions, the times its condition held and the misses of a two-bit saturating
+// predictor of its own (states 0-3, taken from 2, starting at 1): deterministic and the same on every
+// machine, so it ranks the sites against each other; it is not a model of any CPU's predictor.
+#define H2J_BRANCH_SITES(X)                                                                               \
+    X(last_x_max) X(last_x_bin) X(last_y_max) X(last_y_bin) X(last_x_suffix) X(last_y_suffix)             \
+    X(sub_block_loop) X(csbf_coded_range) X(sub_block_uncoded) X(is_last_sub_block) X(sig_scan)           \
+    X(sig_scan_bins) X(sig_loop) X(infer_dc) X(sub_block_empty) X(one_coef_split) X(one_coef_g1)          \
+    X(one_coef_g2) X(g1_second_bin) X(g1_loop) X(g1_any) X(signs_gt2) X(escape_loop) X(output_loop)       \
+    X(decision_refill) X(bypass_refill) X(tt_split_coded) X(tt_split) X(tt_chroma_cbf_read)               \
+    X(tt_cbf_cb_coded) X(tt_cbf_cr_coded) X(tu_qp_delta) X(tu_chroma_blocks) X(tu_chroma_4x4) X(tb_cbf)   \
+    X(cu_part_coded) X(cu_prev_intra) X(cu_mpm_idx0) X(cu_mpm_idx1) X(cu_cand_equal) X(cu_cand_lt2)       \
+    X(cu_cand_sort) X(cu_rem_ge_cand) X(cu_chroma_mode) X(cu_qp_patch_loop) X(cq_split_coded)             \
+    X(cq_split)
+enum BranchSite {
+#define H2J_X(n) BS_##n,
+    H2J_BRANCH_SITES(H2J_X)
+#undef H2J_X
+    BS_COUNT
+};
+struct BranchSiteStat {
+    unsigned long long exec, taken, miss;
+    unsigned state;  // the predictor, biased by one so that zero-initialised storage starts at 1
+};
+extern thread_local BranchSiteStat g_bsite[BS_COUNT];
+inline bool branch_site(BranchSite s, bool taken) {
+    BranchSiteStat& b = g_bsite[s];
+    const unsigned st = b.state ^ 1u;  // 0-3
+    b.exec++;
+    b.taken += taken;
+    b.miss += (st >= 2) != taken;
+    b.state = (taken ? (st < 3 ? st + 1 : 3u) : (st > 0 ? st - 1 : 0u)) ^ 1u;
+    return taken;
+}
+#ifdef H2J_NO_BRANCH_SITES  // `-b`'s hardware counters without the site counters' own cost (no `-B`)
+#define H2J_BR(site, cond) (cond)
+#else
+#define H2J_BR(site, cond) (::h2j::branch_site(::h2j::BS_##site, (cond)))
+#endif
 #else
 #define H2J_COUNT(v, n) ((void)0)
 #define H2J_STAT(f, n) ((void)0)
+#define H2J_BR(site, cond) (cond)
+#endif
+
+// a select whose condition no predictor can learn: keeps clang from turning it into a branch
+#if defined(__clang__)
+#define H2J_UNPREDICTABLE(c) __builtin_unpredictable(c)
+#else
+#define H2J_UNPREDICTABLE(c) (c)
 #endif
 
 // Tables are internal to the library: hidden, so the -fPIC code reaches them RIP-relative and not
@@ -128,12 +175,12 @@ public:
         range_ = r;
         bits_ -= static_cast<int>(sh);
         ctx = nx;
-        if (bits_ < 0) refill();
+        if (H2J_BR(decision_refill, bits_ < 0)) refill();
         return static_cast<int>((st & 1) ^ is_lps);
     }
     __attribute__((always_inline)) int bypass_b() {
         H2J_COUNT(g_bins_byp, 1);
-        if (--bits_ < 0) refill();
+        if (H2J_BR(bypass_refill, --bits_ < 0)) refill();
         const uint64_t scaled = static_cast<uint64_t>(range_) << bits_;
         const bool one = value_ >= scaled;
         value_ -= one ? scaled : 0;
@@ -200,6 +247,24 @@ public:
     uint32_t bypass_bits_o(int n) { return bypass_bits_b(n); }
     __attribute__((always_inline)) int terminate() { return kInlineRefill ? terminate_b() : terminate_o(); }
     int terminate_o() { return terminate_b(); }
+    // Ahead of a run of bins (a coefficient sub-block): bring the look-ahead to 24 bits or more
+    // without a branch on its state -- the next word is always loaded and taken by selects.  The
+    // refill test inside the bins stays (a sub-block can use more than 24 bits) but is then almost
+    // never true, where it was a misprediction every 60 bins.  bits_ stays <= 23 + 32 = 55, the
+    // same bound bypass_batch's refill has: the 9-bit offset above it still fits the 64-bit window.
+    // The last three bytes of the buffer are left to refill().
+    __attribute__((always_inline)) void top_up() {
+        if (__builtin_expect(end_ - cur_ < 4, 0)) return;
+        static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the word load below swaps a little-endian word");
+        uint32_t w;
+        __builtin_memcpy(&w, cur_, 4);
+        w = __builtin_bswap32(w);
+        const bool need = bits_ < 24;
+        const uint64_t nv = (value_ << 32) | w;
+        value_ = H2J_UNPREDICTABLE(need) ? nv : value_;
+        bits_ += H2J_UNPREDICTABLE(need) ? 32 : 0;
+        cur_ += H2J_UNPREDICTABLE(need) ? 4 : 0;
+    }
     // After terminate() returned 1 the arithmetic decoder (9.3.4.3.5) has
     // consumed exactly through the flush's final '1' bit; the next
     // byte-aligned syntax (pcm_sample, next substream) starts at the first

@@ -1126,10 +1126,11 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
     H2J_STAT(tbs, 1);
     // unary prefixes; bins k >> shift share a context (the word forwarded in a register, as in
     // the significance loop below)
-    auto last_prefix = [&](CabacState* lc) __attribute__((always_inline)) {
+    auto last_prefix = [&](CabacState* lc, bool is_y) __attribute__((always_inline)) {
+        (void)is_y;  // names the branch sites of the counting build
         int k = 0, pk = 0;
         CabacState pw = lc[0];
-        while (k < maxp) {
+        while (is_y ? H2J_BR(last_y_max, k < maxp) : H2J_BR(last_x_max, k < maxp)) {
             const int ci = k >> shift;
             const CabacState lw = lc[ci];
             lc[pk] = pw;
@@ -1138,19 +1139,19 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             const int b = cc.decision(w);
             pw = w;
             pk = ci;
-            if (!b) break;
+            if (is_y ? H2J_BR(last_y_bin, !b) : H2J_BR(last_x_bin, !b)) break;
             k++;
         }
         lc[pk] = pw;
         return k;
     };
-    int lx = last_prefix(ctx + C_LAST_X + off);
-    int ly = last_prefix(ctx + C_LAST_Y + off);
-    if (lx > 3) {
+    int lx = last_prefix(ctx + C_LAST_X + off, false);
+    int ly = last_prefix(ctx + C_LAST_Y + off, true);
+    if (H2J_BR(last_x_suffix, lx > 3)) {
         int nb = (lx >> 1) - 1;
         lx = (1 << nb) * (2 + (lx & 1)) + static_cast<int>(cc.bypass_bits(nb));
     }
-    if (ly > 3) {
+    if (H2J_BR(last_y_suffix, ly > 3)) {
         int nb = (ly >> 1) - 1;
         ly = (1 << nb) * (2 + (ly & 1)) + static_cast<int>(cc.bypass_bits(nb));
     }
@@ -1172,13 +1173,16 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
     H2J_STAT(dc_only_tb, (lx | ly) == 0);
     int greater1_ctx = 1;
     const bool sdh = p_->sign_hiding != 0;
-    uint32_t out[32 * 32];
+    uint32_t out[32 * 32 + 4];  // (+ the output loop's padding entries)
     int nout = 0;
     const uint16_t* const posTab = g_scan_off[scanIdx][lsb];
     const uint8_t(*const sigtab)[2][16] = g_sigctx[c ? 1 : 0][lsb][scanIdx];
     CabacState* const gt1ctx = ctx + C_GT1 + (c ? 16 : 0);
-    for (int i = lastSub; i >= 0; i--) {
+    for (int i = lastSub; H2J_BR(sub_block_loop, i >= 0); i--) {
         const int xs = sc[lsb][i][0], ys = sc[lsb][i][1];
+        // the window topped up here without a branch: the refill test of the bins below then
+        // almost never fires (it was a misprediction every 60 bins, 28 k per picture)
+        cc.top_up();
         H2J_STAT(sb_visited, 1);
         bool infer_dc = false;
         // the right / lower neighbours' flags: bits sp + 1 (none in column 7) and sp + 8
@@ -1186,22 +1190,25 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         const unsigned csr = static_cast<unsigned>(((csbm >> 1) & 0x7f7f7f7f7f7f7f7full) >> sp) & 1u;
         const unsigned csb = static_cast<unsigned>((csbm >> 8) >> sp) & 1u;
         unsigned coded = 1;
-        if (i < lastSub && i > 0) {
+        if (H2J_BR(csbf_coded_range, i < lastSub && i > 0)) {
             H2J_STAT(csbf_bins, 1);
             coded = static_cast<unsigned>(cc.decision(ctx[C_CSBF + (csr | csb) + (c ? 2 : 0)]));
             infer_dc = true;
         }
         csbm |= static_cast<uint64_t>(coded) << sp;
+        // an uncoded sub-block (only a flag that was read can say so) ends here: one data-dependent
+        // branch on the flag, where "scan?" and "anything found?" below were two on the same datum
+        if (H2J_BR(sub_block_uncoded, !coded)) continue;
         const int prevCsbf = static_cast<int>(csr | (csb << 1));
         unsigned sigmask = 0;  // bit nn
         int nstart = 15;
-        if (i == lastSub) {
+        if (H2J_BR(is_last_sub_block, i == lastSub)) {
             nstart = lastPos - 1;
             sigmask = 1u << lastPos;
             H2J_STAT(dc_last_sb, lastPos == 0);
         }
         // (a last sub-block whose last position is its DC has no significance bin to read)
-        if (coded && nstart >= 0) {
+        if (H2J_BR(sig_scan, nstart >= 0)) {
             const uint8_t* sig = ts_ctx ? kSigTs[c ? 1 : 0] : sigtab[prevCsbf][(xs | ys) ? 1 : 0];
             // bins feed the mask arithmetically (no data-dependent branch per bin).  Consecutive
             // positions often share a context: the word of the previous bin's context stays in a
@@ -1209,12 +1216,12 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             // previous context's word is stored each bin -- a store and reload of the word the
             // next bin needs would put store-to-load forwarding on the decision chain
             unsigned got = 0;
-            if (nstart > 0) {
+            if (H2J_BR(sig_scan_bins, nstart > 0)) {
                 H2J_STAT(sig_bins, nstart);
                 int pidx = sig[nstart];
                 CabacState pw = ctx[pidx];
                 got = static_cast<unsigned>(cc.decision(pw)) << nstart;
-                for (int nn = nstart - 1; nn > 0; nn--) {
+                for (int nn = nstart - 1; H2J_BR(sig_loop, nn > 0); nn--) {
                     const int idx = sig[nn];
                     const CabacState lw = ctx[idx];
                     ctx[pidx] = pw;
@@ -1226,14 +1233,14 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
                 ctx[pidx] = pw;
             }
             sigmask |= got;
-            if (infer_dc && got == 0) {
+            if (H2J_BR(infer_dc, infer_dc && got == 0)) {
                 sigmask |= 1u;  // nn == 0 inferred
             } else {
                 H2J_STAT(sig0_bins, 1);
                 if (cc.decision(ctx[sig[0]])) sigmask |= 1u;
             }
         }
-        if (!sigmask) continue;
+        if (H2J_BR(sub_block_empty, !sigmask)) continue;  // the DC sub-block of a block whose levels all lie elsewhere
         H2J_STAT(sb_coded, 1);
         // greater1 / greater2
         int ctxSet = (i == 0 || c > 0) ? 0 : 2;
@@ -1247,7 +1254,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             H2J_STAT(gt1_bins, nc < 8 ? nc : 8);
         }
 #endif
-        if ((sigmask & (sigmask - 1)) == 0) {
+        if (H2J_BR(one_coef_split, (sigmask & (sigmask - 1)) == 0)) {
             // One coefficient (54 % of the coded sub-blocks of the 149 KB set), as straight-line
             // code: one greater1 bin on greater1Ctx 1, greater2 if it is set, one sign, and the
             // remaining level only after greater2 (baseLevel 3).  Sign hiding needs two positions.
@@ -1258,13 +1265,13 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             const int g1 = cc.decision(gt1ctx[ctxSet * 4 + 1]);
             greater1_ctx = g1 ^ 1;
             int lvl = 1 + g1, g2 = 0;
-            if (g1) {
+            if (H2J_BR(one_coef_g1, g1 != 0)) {
                 H2J_STAT(gt2_bins, 1);
                 g2 = cc.decision(ctx[C_GT2 + ctxSet + (c ? 4 : 0)]);
                 lvl += g2;
             }
             const int neg = cc.bypass();
-            if (g2) {
+            if (H2J_BR(one_coef_g2, g2 != 0)) {
                 H2J_STAT(one_coef_esc, 1);
                 H2J_STAT(one_coef_esc_price, price);
                 H2J_STAT(one_coef_esc_tskip, (tu.flags & H2J_TU_TSKIP) != 0);
@@ -1313,8 +1320,8 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
                 numG1++;
             };
             if (m) bin(w1);
-            if (m) bin(w2);
-            while (m && numG1 < 8) bin(w3);
+            if (H2J_BR(g1_second_bin, m != 0)) bin(w2);
+            while (H2J_BR(g1_loop, m && numG1 < 8)) bin(w3);
             g1c[0] = w0;
             g1c[1] = w1;
             g1c[2] = w2;
@@ -1325,7 +1332,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         if (g1mask) lastG1 = 31 - __builtin_clz(g1mask);
         const bool hidden = !cu_bypass_ && !no_sdh && (lastSig - firstSig > 3);
         int g2 = 0;
-        if (lastG1 != -1) {
+        if (H2J_BR(g1_any, lastG1 != -1)) {
             H2J_STAT(gt2_bins, 1);
             g2 = cc.decision(ctx[C_GT2 + ctxSet + (c ? 4 : 0)]);
         }
@@ -1338,7 +1345,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         H2J_STAT(sign_batch_sbs, ns > 1);
         H2J_STAT(sign_single_sbs, ns <= 1);
         H2J_STAT(sign_pair, ns == 2);
-        const uint32_t q = ns > 2 ? cc.bypass_batch(ns) : cc.bypass_bits(ns);
+        const uint32_t q = H2J_BR(signs_gt2, ns > 2) ? cc.bypass_batch(ns) : cc.bypass_bits(ns);
         uint32_t qs = ns ? q << (32 - ns) : 0u;
         // positions that carry coeff_abs_level_remaining (baseLevel reached its cap): greater1
         // set (greater2 set for the one position that has it) among the first eight, and every
@@ -1351,7 +1358,7 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         int remv[16] = {};
         int rice = price ? *stat / 4 : 0;
         bool stat_done = false;
-        for (unsigned e = esc; e;) {
+        for (unsigned e = esc; H2J_BR(escape_loop, e != 0);) {
             const int nn = 31 - __builtin_clz(e);
             e &= ~(1u << nn);
             const int baseL = 1 + ((g1mask >> nn) & 1) + (nn == lastG1 ? g2 : 0);
@@ -1368,9 +1375,16 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
         }
         // sign data hiding: the lowest position (processed last) flips when the level sum is odd
         const int flip_last = (sdh && hidden) ? 1 : 0;
+        // Four entries per trip: 82 % of these sub-blocks hold two to four coefficients, so the exit
+        // is "one trip" for them where a trip per coefficient left it on a count of 2, 3, 4, ...; the
+        // entries past the last coefficient (position 0 again, after the mask ran empty) are written
+        // behind nout and overwritten by the next sub-block.  Only the first entry with an empty
+        // mask, the true lowest position, must see the parity: the others' values do not matter.
         int sumAbs = 0;
-        for (unsigned mm = sigmask; mm;) {
-            const int nn = 31 - __builtin_clz(mm);
+        unsigned mm = sigmask;
+        uint32_t* o = out + nout;
+        auto entry = [&]() __attribute__((always_inline)) {
+            const int nn = 31 - __builtin_clz(mm | 1u);
             mm &= ~(1u << nn);
             const int lvl = 1 + ((g1mask >> nn) & 1) + (nn == lastG1 ? g2 : 0) + remv[nn];
             sumAbs += lvl;
@@ -1379,8 +1393,15 @@ void HevcParser::residual(int log2n, int c, int pred_mode, h2j_tu& tu) {
             int v = neg ? -lvl : lvl;
             if (v > 32767) v = 32767;
             if (v < -32768) v = -32768;
-            out[nout++] = (static_cast<uint32_t>(sb_off + posTab[nn]) << 16) | static_cast<uint16_t>(v);
-        }
+            *o++ = (static_cast<uint32_t>(sb_off + posTab[nn]) << 16) | static_cast<uint16_t>(v);
+        };
+        do {
+            entry();
+            entry();
+            entry();
+            entry();
+        } while (H2J_BR(output_loop, mm != 0));
+        nout += __builtin_popcount(sigmask);
     }
     cc_ = cc;
     const uint32_t base = static_cast<uint32_t>(job_->coefs.size());
@@ -1416,7 +1437,7 @@ void HevcParser::emit_tu(int x, int y, int log2n, int c, int mode, uint8_t flags
     tu.qpy = 0;
     tu.ncoef = 0;
     tu.coef = 0;
-    if (cbf) {
+    if (H2J_BR(tb_cbf, cbf)) {
         if (rext_) residual<true>(log2n, c, mode, tu);
         else residual<false>(log2n, c, mode, tu);
     }
@@ -1424,7 +1445,7 @@ void HevcParser::emit_tu(int x, int y, int log2n, int c, int mode, uint8_t flags
 
 void HevcParser::transform_unit(int x0, int y0, int xb, int yb, int log2n, int blk, int cbf_l, int cbf_cb,
                                 int cbf_cr, int cm, int cux, int cuy, int log2cb) {
-    if ((cbf_l || cbf_cb || cbf_cr) && p_->cu_qp_delta && !is_qpd_coded_) {
+    if (H2J_BR(tu_qp_delta, (cbf_l || cbf_cb || cbf_cr) && p_->cu_qp_delta && !is_qpd_coded_)) {
         int v = 0;
         if (dec(C_QP_DELTA)) {
             v = 1;
@@ -1466,11 +1487,11 @@ void HevcParser::transform_unit(int x0, int y0, int xb, int yb, int log2n, int b
     if ((job_->tus.back().flags & (H2J_TU_TSKIP | H2J_TU_BYPASS)) != 0) job_->tus.back().flags &= ~H2J_TU_DST;
     if (err_) return;
     uint8_t cfl = cu_bypass_ ? (H2J_TU_BYPASS | H2J_TU_NOFILT) : 0;
-    if (log2n > 2) {
+    if (H2J_BR(tu_chroma_blocks, log2n > 2)) {
         emit_tu(x0 >> 1, y0 >> 1, log2n - 1, 1, cm, cfl, cbf_cb != 0, cm);
         if (err_) return;
         emit_tu(x0 >> 1, y0 >> 1, log2n - 1, 2, cm, cfl, cbf_cr != 0, cm);
-    } else if (blk == 3) {
+    } else if (H2J_BR(tu_chroma_4x4, blk == 3)) {
         emit_tu(xb >> 1, yb >> 1, 2, 1, cm, cfl, cbf_cb != 0, cm);
         if (err_) return;
         emit_tu(xb >> 1, yb >> 1, 2, 2, cm, cfl, cbf_cr != 0, cm);
@@ -1481,19 +1502,19 @@ void HevcParser::transform_tree(int x0, int y0, int xb, int yb, int log2n, int d
                                 int intra_split, int pcb, int pcr, int cm, int cux, int cuy, int log2cb) {
     if (err_) return;
     int split;
-    if (log2n <= s_->log2_max_tb && log2n > s_->log2_min_tb && depth < max_depth && !(intra_split && depth == 0))
+    if (H2J_BR(tt_split_coded, log2n <= s_->log2_max_tb && log2n > s_->log2_min_tb && depth < max_depth && !(intra_split && depth == 0)))
         split = dec(C_SPLIT_TF + 5 - log2n);
     else
         split = log2n > s_->log2_max_tb || (intra_split && depth == 0);
     int cbf_cb = 0, cbf_cr = 0;
-    if (log2n > 2) {
-        if (depth == 0 || pcb) cbf_cb = dec(C_CBF_CHROMA + depth);
-        if (depth == 0 || pcr) cbf_cr = dec(C_CBF_CHROMA + depth);
+    if (H2J_BR(tt_chroma_cbf_read, log2n > 2)) {
+        if (H2J_BR(tt_cbf_cb_coded, depth == 0 || pcb)) cbf_cb = dec(C_CBF_CHROMA + depth);
+        if (H2J_BR(tt_cbf_cr_coded, depth == 0 || pcr)) cbf_cr = dec(C_CBF_CHROMA + depth);
     } else {
         cbf_cb = pcb;
         cbf_cr = pcr;
     }
-    if (split) {
+    if (H2J_BR(tt_split, split != 0)) {
         if (log2n <= 2) { err_ = -23; return; }
         int h = 1 << (log2n - 1);
         transform_tree(x0, y0, x0, y0, log2n - 1, depth + 1, 0, max_depth, intra_split, cbf_cb, cbf_cr, cm, cux, cuy, log2cb);
@@ -1568,7 +1589,7 @@ void HevcParser::coding_unit(int x0, int y0, int log2cb) {
     cu_bypass_ = 0;
     if (p_->transquant_bypass) cu_bypass_ = dec(C_TQ_BYPASS);
     int part_nxn = 0;
-    if (log2cb == s_->log2_min_cb) part_nxn = !dec(C_PART_MODE);
+    if (H2J_BR(cu_part_coded, log2cb == s_->log2_min_cb)) part_nxn = !dec(C_PART_MODE);
     qp_y_ = qp_wrap(qg_pred_ + qpd_val_ + 52 + 2 * qpbd) - qpbd;
     set_qp(x0, y0, n, qp_y_);
     int pcm = 0;
@@ -1581,8 +1602,8 @@ void HevcParser::coding_unit(int x0, int y0, int log2cb) {
         int prev[4], mpm[4] = {0, 0, 0, 0}, rem[4] = {0, 0, 0, 0};
         for (int i = 0; i < np; i++) prev[i] = dec(C_PREV_INTRA);
         for (int i = 0; i < np; i++) {
-            if (prev[i]) {
-                if (cc_.bypass()) mpm[i] = cc_.bypass() ? 2 : 1;
+            if (H2J_BR(cu_prev_intra, prev[i] != 0)) {
+                if (H2J_BR(cu_mpm_idx0, cc_.bypass() != 0)) mpm[i] = H2J_BR(cu_mpm_idx1, cc_.bypass() != 0) ? 2 : 1;
             } else {
                 rem[i] = static_cast<int>(cc_.bypass_bits(5));
             }
@@ -1594,8 +1615,8 @@ void HevcParser::coding_unit(int x0, int y0, int log2cb) {
             if (same_region(xp, yp, xp, yp - 1) && ((yp - 1) >> log2ctb) == (yp >> log2ctb))
                 cb = ipm_[((yp - 1) >> 2) * mw + (xp >> 2)];
             int cand[3];
-            if (ca == cb) {
-                if (ca < 2) { cand[0] = 0; cand[1] = 1; cand[2] = 26; }
+            if (H2J_BR(cu_cand_equal, ca == cb)) {
+                if (H2J_BR(cu_cand_lt2, ca < 2)) { cand[0] = 0; cand[1] = 1; cand[2] = 26; }
                 else { cand[0] = ca; cand[1] = 2 + ((ca + 29) % 32); cand[2] = 2 + ((ca - 2 + 1) % 32); }
             } else {
                 cand[0] = ca;
@@ -1606,17 +1627,17 @@ void HevcParser::coding_unit(int x0, int y0, int log2cb) {
             if (prev[i]) {
                 mode = cand[mpm[i]];
             } else {
-                if (cand[0] > cand[1]) std::swap(cand[0], cand[1]);
-                if (cand[0] > cand[2]) std::swap(cand[0], cand[2]);
-                if (cand[1] > cand[2]) std::swap(cand[1], cand[2]);
+                if (H2J_BR(cu_cand_sort, cand[0] > cand[1])) std::swap(cand[0], cand[1]);
+                if (H2J_BR(cu_cand_sort, cand[0] > cand[2])) std::swap(cand[0], cand[2]);
+                if (H2J_BR(cu_cand_sort, cand[1] > cand[2])) std::swap(cand[1], cand[2]);
                 mode = rem[i];
                 for (int k = 0; k < 3; k++)
-                    if (mode >= cand[k]) mode++;
+                    if (H2J_BR(cu_rem_ge_cand, mode >= cand[k])) mode++;
             }
             set_map(ipm_, xp, yp, pb, static_cast<uint8_t>(mode));
         }
         int icpm = 4;
-        if (dec(C_CHROMA_MODE)) icpm = static_cast<int>(cc_.bypass_bits(2));
+        if (H2J_BR(cu_chroma_mode, dec(C_CHROMA_MODE) != 0)) icpm = static_cast<int>(cc_.bypass_bits(2));
         const int lm = ipm_[(y0 >> 2) * mw + (x0 >> 2)];
         int cm;
         if (icpm == 4) cm = lm;
@@ -1638,7 +1659,7 @@ void HevcParser::coding_unit(int x0, int y0, int log2cb) {
         if (qpi > 57) qpi = 57;
         qpc[k] = chroma_qp_table(qpi) + qpbd;
     }
-    for (size_t t = static_cast<size_t>(cu_tu_begin_); t < job_->tus.size(); t++) {
+    for (size_t t = static_cast<size_t>(cu_tu_begin_); H2J_BR(cu_qp_patch_loop, t < job_->tus.size()); t++) {
         h2j_tu& tu = job_->tus[t];
         tu.qpy = static_cast<int8_t>(qp_y_);
         tu.qp = static_cast<int8_t>(tu.c == 0 ? qpy : qpc[tu.c - 1]);
@@ -1650,7 +1671,7 @@ void HevcParser::coding_quadtree(int x0, int y0, int log2cb, int depth) {
     if (err_) return;
     const int n = 1 << log2cb;
     int split;
-    if (x0 + n <= W && y0 + n <= H && log2cb > s_->log2_min_cb) {
+    if (H2J_BR(cq_split_coded, x0 + n <= W && y0 + n <= H && log2cb > s_->log2_min_cb)) {
         int inc = 0;
         if (same_region(x0, y0, x0 - 1, y0) && ctd_[(y0 >> 2) * mw + ((x0 - 1) >> 2)] > depth) inc++;
         if (same_region(x0, y0, x0, y0 - 1) && ctd_[((y0 - 1) >> 2) * mw + (x0 >> 2)] > depth) inc++;
@@ -1661,7 +1682,7 @@ void HevcParser::coding_quadtree(int x0, int y0, int log2cb, int depth) {
     if ((p_->cu_qp_delta && log2cb >= log2ctb - p_->diff_cu_qp_delta_depth) || (!p_->cu_qp_delta && log2cb == log2ctb))
         qg_start(x0, y0);
     if (cur_->cu_chroma_qp_offset_enabled && log2cb >= log2ctb - p_->cqo_depth) cqo_coded_ = false;
-    if (split) {
+    if (H2J_BR(cq_split, split != 0)) {
         const int h = n >> 1;
         coding_quadtree(x0, y0, log2cb - 1, depth + 1);
         if (x0 + h < W) coding_quadtree(x0 + h, y0, log2cb - 1, depth + 1);

@@ -31,6 +31,7 @@
 namespace h2j {
 thread_local unsigned long long g_bins_ctx = 0, g_bins_byp = 0;
 thread_local ResidualStats g_rstat = {};
+thread_local BranchSiteStat g_bsite[BS_COUNT] = {};
 }
 namespace {
 // -b: a hardware counter of this thread (user mode), or -1 where the kernel does not allow one
@@ -79,11 +80,11 @@ int main(int argc, char** argv) {
     h2j_sample::start();
 #endif
     if (argc < 2) {
-        std::fprintf(stderr, "usage: parse_bench file... [-r reps] [-t threads] [-d (output digest)] [-m] [-s] [-p n] [-b (residual breakdown)]\n");
+        std::fprintf(stderr, "usage: parse_bench file... [-r reps] [-t threads] [-d (output digest)] [-m] [-s] [-p n] [-b (residual breakdown)] [-B (branch sites)]\n");
         return 2;
     }
     int reps = 3, threads = 1, pthreads = 1;
-    bool want_digest = false, want_hist = false, want_min = false, want_breakdown = false;
+    bool want_digest = false, want_hist = false, want_min = false, want_breakdown = false, want_sites = false;
     std::vector<std::vector<uint8_t>> streams;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -97,6 +98,10 @@ int main(int argc, char** argv) {
         }
         if (a == "-b") {  // residual-syntax breakdown (-DH2J_CABAC_COUNT builds)
             want_breakdown = true;
+            continue;
+        }
+        if (a == "-B") {  // branch-site table of the slice-data path (-DH2J_CABAC_COUNT builds)
+            want_sites = true;
             continue;
         }
         if (a == "-m") {  // min-of-reps per stream (robust to a noisy host): sum of per-stream minima
@@ -190,6 +195,46 @@ int main(int argc, char** argv) {
         return 0;
 #else
         std::fprintf(stderr, "-b needs a -DH2J_CABAC_COUNT build\n");
+        return 2;
+#endif
+    }
+    if (want_sites) {
+#if defined(H2J_CABAC_COUNT) && !defined(H2J_NO_BRANCH_SITES)
+        // every data-dependent branch of the HEVC slice-data path as a named site (cabac.h): how often it
+        // ran, how often its condition held, and the misses of a two-bit predictor simulated per site --
+        // the same on every machine, so the table ranks the sites; one pass over the streams on this thread
+        static const char* const kSite[h2j::BS_COUNT] = {
+#define H2J_X(n) #n,
+            H2J_BRANCH_SITES(H2J_X)
+#undef H2J_X
+        };
+        h2j::FrameJob job;
+        unsigned long long digest = 0;
+        for (const auto& s : streams) {
+            const int codec = h2j::detect_codec(s.data(), s.size());
+            const int rc = codec == 265 ? h2j::hevc_parse_picture(s.data(), s.size(), job)
+                                        : h2j::h264_parse_picture(s.data(), s.size(), job);
+            if (rc) {
+                std::fprintf(stderr, "parse error %d: %s\n", rc, job.message.c_str());
+                return 1;
+            }
+            digest += job_digest(job);
+        }
+        const double nf = static_cast<double>(streams.size());
+        std::printf("branch sites of %zu pictures, digest %016llx\n", streams.size(), digest);
+        std::printf("%-22s %14s %14s %14s %12s\n", "site", "executed", "taken", "sim_misses", "misses/pic");
+        unsigned long long te = 0, tt = 0, tm = 0;
+        for (int k = 0; k < h2j::BS_COUNT; k++) {
+            const h2j::BranchSiteStat& b = h2j::g_bsite[k];
+            std::printf("%-22s %14llu %14llu %14llu %12.0f\n", kSite[k], b.exec, b.taken, b.miss, b.miss / nf);
+            te += b.exec;
+            tt += b.taken;
+            tm += b.miss;
+        }
+        std::printf("%-22s %14llu %14llu %14llu %12.0f\n", "all_sites", te, tt, tm, tm / nf);
+        return 0;
+#else
+        std::fprintf(stderr, "-B needs a -DH2J_CABAC_COUNT build (without -DH2J_NO_BRANCH_SITES)\n");
         return 2;
 #endif
     }
