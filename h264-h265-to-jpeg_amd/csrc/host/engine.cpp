@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "bitstream.h"
+#include "heif.h"
 #include "jpeg_writer.h"
 #include "out_opts.h"
 
@@ -39,6 +40,9 @@ extern "C" int h2j_gpu_rgb(const h2j_gpu_batch*, const h2j_rgb*, const int32_t*,
 namespace h2j {
 
 int parse_any(const uint8_t* d, size_t n, FrameJob& job) {
+    // a job slot is reused from batch to batch: what an earlier HEIF input left in it goes before anything is parsed
+    if (job.demuxed.capacity()) std::vector<uint8_t>().swap(job.demuxed);
+    if (is_heif(d, n)) return heif_parse_picture(d, n, job);  // its items as Annex-B streams, then the parsers below
     const int codec = detect_codec(d, n);
     if (codec == 265) return hevc_parse_picture(d, n, job);
     if (codec == 264) return h264_parse_picture(d, n, job);

@@ -5,6 +5,7 @@
 
 #include "bitstream.h"
 #include "engine.h"
+#include "heif.h"
 #include "out_opts.h"
 
 using h2j::Engine;
@@ -388,6 +389,7 @@ int h2j_crop_window6(int w, int h, const h2j_out_opts6* o, int sei_orient, int32
 
 int h2j_stream_orientation(const uint8_t* data, size_t size) {
     if (!data) return -1;
+    if (h2j::is_heif(data, size)) return h2j::heif_orientation(data, size);
     const int codec = h2j::detect_codec(data, size);
     if (codec != 264 && codec != 265) return -100;
     return h2j::stream_display_orientation(data, size, codec);

@@ -587,6 +587,7 @@ public:
         ctbs_ = proto.ctbs_;
     }
     int run(const uint8_t* data, size_t size, int threads);
+    int run_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, int cols, int out_w, int out_h, int threads);
 
 private:
     HevcParser(const HevcParser&) = default;
@@ -2120,7 +2121,198 @@ int HevcParser::run(const uint8_t* data, size_t size, int threads) {
     return 0;
 }
 
+// A HEIF grid as one picture (DESIGN.md "HEIF input"): rows x cols independently coded tile pictures of one size
+// are, sample for sample, the tiles of one canvas picture of cols * tw x rows * th whose PPS has uniform tiles and
+// loop_filter_across_tiles_enabled_flag 0, cropped to out_w x out_h by its conformance window.  A tile border stops
+// intra prediction, the CABAC contexts, the QP predictor, deblocking and SAO exactly where the tile picture's edge
+// did.  Each tile picture's slices become the canvas slices of that tile; each is decoded as decode_tile decodes a
+// tile, into records of its own, appended in canvas decoding order whatever the thread count.
+int HevcParser::run_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, int cols, int out_w, int out_h, int threads) {
+    init_scans();
+    auto fail = [&](int code, const char* m) {
+        job_->message = m;
+        return code;
+    };
+    if (rows < 1 || cols < 1 || rows > 64 || cols > 64) return fail(-9, "HEIF grid: more than 64 tile rows or columns");
+    const int T = rows * cols;
+    std::vector<std::vector<uint8_t>> seg;  // per canvas slice: its slice data (+8 zero bytes)
+    std::vector<int> seg_tile;              // and its tile
+    std::vector<uint8_t> ps0[2], ps[2];     // the SPS [0] and PPS [1] NAL units in front of a tile picture
+    std::vector<Nal> nals;
+    int tw = 0, th = 0;
+    sh_.reserve(256);
+    for (int t = 0; t < T; t++) {
+        nals.clear();
+        split_annexb(tiles[t], sizes[t], nals);
+        rbsp_.resize(sizes[t] + 16);
+        ps[0].clear();
+        ps[1].clear();
+        bool have_pic = false;
+        const SliceHdr* prev = nullptr;
+        for (const Nal& nal : nals) {
+            if (nal.n < 2) continue;
+            const int type = (nal.p[0] >> 1) & 63;
+            const size_t rn = unescape_rbsp(nal.p + 2, nal.n - 2, rbsp_.data());
+            BitReader b(rbsp_.data(), rn);
+            if (type == 33 || type == 34) {
+                if (have_pic) break;
+                std::vector<uint8_t>& set = ps[type - 33];
+                for (int k = 24; k >= 0; k -= 8) set.push_back(static_cast<uint8_t>(nal.n >> k));
+                set.insert(set.end(), nal.p, nal.p + nal.n);
+                if (t > 0) continue;  // tile 0's are the grid's: the others must equal them byte for byte
+                if (type == 33) {
+                    const int e = parse_sps(b, sps_);
+                    if (e < 0)
+                        return fail(-2, e == -12 ? "unsupported bit depth (FFmpeg 4.3 has no HEVC 4:2:0 format at it)"
+                                                 : "unsupported or invalid SPS");
+                } else if (parse_pps(b, pps_, sps_) < 0) {
+                    return fail(-3, "invalid PPS");
+                }
+            } else if (type <= 21) {
+                if (type >= 10 && type <= 15) continue;
+                const int first = (rbsp_[0] >> 7) & 1;
+                if (first && have_pic) break;
+                if (!first && !have_pic) continue;
+                if (t > 0 && !have_pic && ps[0] != ps0[0]) return fail(-9, "HEIF grid: tiles carry different SPS");
+                if (t > 0 && !have_pic && ps[1] != ps0[1]) return fail(-9, "HEIF grid: tiles carry different PPS");
+                if (sh_.size() >= 255) return fail(-4, "too many slices");
+                sh_.push_back(SliceHdr());
+                SliceHdr& sh = sh_.back();
+                const int r = parse_slice_header(b, type, sh, prev);
+                if (r < 0)
+                    return fail(r == -2 ? -5 : -6, r == -2 ? "non-intra first picture (P/B slices) unsupported" : "invalid slice header");
+                if (sh.dependent) return fail(-9, "HEIF grid: a tile picture uses dependent slice segments");
+                if (seg.empty()) {
+                    p_ = &pps_[sh.pps_id];
+                    s_ = &sps_[p_->sps_id];
+                    ps0[0] = ps[0];
+                    ps0[1] = ps[1];
+                    tw = s_->width;
+                    th = s_->height;
+                    const int cs = 1 << s_->log2_ctb;
+                    if (p_->tiles || p_->wpp) return fail(-9, "HEIF grid: a tile picture uses tiles or wavefront parallel processing");
+                    if (s_->conf_l || s_->conf_r || s_->conf_t || s_->conf_b)
+                        return fail(-9, "HEIF grid: a tile picture's conformance window is not its coded size");
+                    if ((tw % cs) || (th % cs)) return fail(-9, "HEIF grid: tile size is not a multiple of the CTB size");
+                    if (static_cast<long>(cols) * tw > 8192 || static_cast<long>(rows) * th > 8192)
+                        return fail(-9, "HEIF grid: canvas larger than 8192 x 8192");
+                    const int W2 = out_w & ~1, H2 = out_h & ~1;  // odd sizes round down, as a 4:2:0 conformance window does
+                    if (out_w > cols * tw || out_h > rows * th || out_w <= (cols - 1) * tw || out_h <= (rows - 1) * th)
+                        return fail(-9, "HEIF grid: output size does not end in the last tile row and column");
+                    // an odd size one sample past a tile border is legal, but rounded down nothing of the last tile
+                    // column or row would be shown: refused by name, not shown as a picture one column short
+                    if (W2 <= (cols - 1) * tw || H2 <= (rows - 1) * th)
+                        return fail(-9, "HEIF grid: odd output size one sample past a tile border is unsupported");
+                }
+                if (&pps_[sh.pps_id] != p_) return fail(-6, "PPS change inside picture");
+                if (have_pic ? sh.address <= prev->address : sh.address != 0) return fail(-6, "invalid slice header");
+                const size_t off = b.byte_pos();
+                if (off > rn) return fail(-6, "truncated slice");
+                seg.emplace_back(rbsp_.begin() + static_cast<long>(off), rbsp_.begin() + static_cast<long>(rn));
+                seg.back().resize(seg.back().size() + 8, 0);
+                seg_tile.push_back(t);
+                prev = &sh_.back();
+                have_pic = true;
+            } else if (type == 35 && have_pic) {
+                break;
+            }
+        }
+        if (!have_pic) return fail(-8, "no picture found");
+    }
+    // the canvas parameter sets: the tiles' own, the size and the tile grid replaced
+    const int pid = sh_[0].pps_id, sid = pps_[pid].sps_id;
+    Sps& cs = sps_[sid];
+    Pps& cp = pps_[pid];
+    const int tcw = tw >> cs.log2_ctb, tn = tcw * (th >> cs.log2_ctb);
+    cs.width = cols * tw;
+    cs.height = rows * th;
+    cs.conf_r = cs.width - (out_w & ~1);
+    cs.conf_b = cs.height - (out_h & ~1);
+    cp.tiles = T > 1;
+    cp.ntc = cols;
+    cp.ntr = rows;
+    cp.uniform = 1;
+    cp.lf_across_tiles = T > 1 ? 0 : 1;
+    p_ = &cp;
+    s_ = &cs;
+    if (!setup_picture()) return fail(-6, "invalid tile grid");
+    job_->reorder_delay = s_->num_reorder_pics > 0;
+    // canvas slices: slice_segment_address in the tile picture's raster scan is the offset in the tile's tile scan
+    const int ns = static_cast<int>(sh_.size());
+    std::vector<int> ts0(ns), ts1(ns);
+    for (int i = 0; i < ns; i++) {
+        ts0[i] = seg_tile[i] * tn + sh_[i].address;
+        ts1[i] = (i + 1 < ns && seg_tile[i + 1] == seg_tile[i]) ? seg_tile[i] * tn + sh_[i + 1].address : (seg_tile[i] + 1) * tn;
+    }
+    for (int i = 0; i < ns; i++) {
+        SliceHdr& sh = sh_[i];
+        sh.address = sh.slice_addr_rs = ts2rs_[ts0[i]];
+        for (int ts = ts0[i]; ts < ts1[i]; ts++) {  // ownership up front: edge flags compare slice addresses across borders
+            ctb_slice_[ts2rs_[ts]] = i;
+            ctb_addr_rs_[ts2rs_[ts]] = sh.slice_addr_rs;
+        }
+        h2j_slice rec{};
+        rec.beta_offset = static_cast<int8_t>(sh.beta_offset);
+        rec.tc_offset = static_cast<int8_t>(sh.tc_offset);
+        rec.sao_luma = static_cast<uint8_t>(sh.sao_luma);
+        rec.sao_chroma = static_cast<uint8_t>(sh.sao_chroma);
+        rec.lf_across_slices = static_cast<uint8_t>(sh.lf_across_slices);
+        rec.deblock_disabled = static_cast<uint8_t>(sh.deblock_disabled);
+        rec.slice_addr_rs = sh.slice_addr_rs;
+        job_->slices.push_back(rec);
+    }
+    std::vector<FrameJob> part(ns);
+    const int nw = std::max(1, std::min(threads, ns));
+    std::vector<std::unique_ptr<HevcParser>> wk(nw);
+    {
+        // the workers read and write this parser's maps through its pointers: the storage itself (three bytes per
+        // 4x4 block of a canvas of up to 8192 x 8192) steps aside while they are copied from this parser
+        std::vector<int8_t> qp;
+        std::vector<uint8_t> ipm, ctd;
+        qp.swap(qp_store_);
+        ipm.swap(ipm_store_);
+        ctd.swap(ctd_store_);
+        for (int w = 0; w < nw; w++) {
+            wk[w].reset(new HevcParser(*this, true));
+            wk[w]->p_ = &wk[w]->pps_[pid];
+            wk[w]->s_ = &wk[w]->sps_[sid];
+        }
+        qp.swap(qp_store_);
+        ipm.swap(ipm_store_);
+        ctd.swap(ctd_store_);
+    }
+    std::vector<int> rc(ns, 0);
+    std::atomic<int> next(0);
+    auto work = [&](HevcParser& P) {
+        for (int i = next++; i < ns; i = next++) {
+            P.job_ = &part[i];
+            P.err_ = 0;
+            // a tile picture's slice ends in end_of_slice_segment_flag, as the last tile of a slice does
+            rc[i] = P.decode_tile(i, ts0[i], ts1[i], true, seg[i].data(), seg[i].data() + (seg[i].size() - 8));
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int w = 1; w < nw; w++) pool.emplace_back(work, std::ref(*wk[w]));
+    work(*wk[0]);
+    for (auto& t : pool) t.join();
+    for (int i = 0; i < ns; i++)
+        if (rc[i] < 0) return fail(-7, "slice data decode error");
+    merge_parts(part);
+    job_->hdr.nslice = static_cast<uint32_t>(job_->slices.size());
+    job_->hdr.topo = (ns != 1 || T > 1) ? 1u : 0u;
+    job_->hdr.ntu = static_cast<uint32_t>(job_->tus.size());
+    return 0;
+}
+
 }  // namespace
+
+int hevc_parse_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, int cols, int out_w, int out_h, FrameJob& job) {
+    job.clear();
+    std::unique_ptr<HevcParser> p(new HevcParser(job));
+    const int r = p->run_grid(tiles, sizes, rows, cols, out_w, out_h, job.threads);
+    job.error = r;
+    return r;
+}
 
 int hevc_parse_picture(const uint8_t* data, size_t size, FrameJob& job) {
     job.clear();

@@ -59,6 +59,10 @@ struct FrameJob {
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;
     int out_base = 0;  // index of the item's first rendition in the batch's output arrays
+    // a HEIF input's items rewritten as Annex-B streams (heif.h), owned here so the parse can outlive the
+    // demuxer; untouched by clear(), which the parsers call on the job they fill, and released by the next
+    // parse_any on this job (HEIF or not), so a reused slot never keeps a large file's bytes
+    std::vector<uint8_t> demuxed;
 
     void clear() {
         hdr = h2j_frame{};
@@ -86,5 +90,12 @@ enum { H2J_SL264_4 = 0, H2J_SL264_8 = 48, H2J_SL264_BYTES = 112 };
 int hevc_parse_picture(const uint8_t* data, size_t size, FrameJob& job);
 // Same for H.264.
 int h264_parse_picture(const uint8_t* data, size_t size, FrameJob& job);
+// A HEIF grid (rows x cols tile pictures as Annex-B streams, raster order; output out_w x out_h) parsed into the
+// job records of one tiled canvas picture.  Tiles parse side by side when job.threads > 1; the records are the same.
+int hevc_parse_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, int cols, int out_w, int out_h, FrameJob& job);
+// A HEIF file (heif.h: is_heif): its primary item demuxed into job.demuxed and parsed by the calls above; irot /
+// imir become job.sei_orient.  heif_orientation: that orientation alone (0, 2..8; negative: the demuxer's status)
+int heif_parse_picture(const uint8_t* data, size_t size, FrameJob& job);
+int heif_orientation(const uint8_t* data, size_t size);
 
 }  // namespace h2j

@@ -12,6 +12,13 @@
  * would bind for throughput, see INTEGRATION.md.
  *
  * Return values: 0 success, < 0 error (message via h2j_engine_error).
+ *
+ * Input: wherever a call takes the bytes of a stream (data / sizes), they are an Annex-B elementary
+ * stream of either codec, or a HEIF / HEIC file (DESIGN.md "HEIF input"): its primary item, a single
+ * hvc1 / avc1 item or a grid of hvc1 tiles decoded as one picture of the grid's output size.  A HEIF
+ * file that cannot be read fails alone with a status in -110..-115 and its own frame-error message.
+ * Its irot / imir properties stand where a stream's display orientation SEI stands (H2J_ORIENT_AUTO,
+ * h2j_stream_orientation): never applied unasked.
  */
 #ifndef H2J_H
 #define H2J_H

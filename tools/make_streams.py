@@ -18,6 +18,7 @@ reconstruction bit-for-bit.
   python tools/make_streams.py f3        -> tests/golden/f3/ (decoder delay, non-IDR / CRA / BLA first pictures)
   python tools/make_streams.py malformed -> tests/golden/malformed/ (out-of-range SPS / slice header values)
   python tools/make_streams.py heavy     -> tests/golden/bench_heavy/hevc1080h_XX.h265 (16 streams, ~100-250 KB)
+  python tools/make_streams.py heif      -> tests/golden/heif/ (tile pictures of HEIF grids, sets a-e, and H.264 tiles)
   python tools/make_streams.py aim       -> tests/golden/bench_aim/hevc1080a_XX.h265 (64 streams, QP 22-37, 110-220 KB)
 """
 import glob
@@ -633,9 +634,70 @@ def fourk(n=4):
         print(f"{path}: qp {qp} -> {nb} B", flush=True)
 
 
+HEIF_SETS = [
+    # HEIF grid tile sets (tests/heif_mux.py wraps them at test time): name, tile w, h, CTB, tiles, bit depth, QP,
+    # options.  The smallest shapes at which a canvas of tiles can still go wrong; QP >= 32 with SAO on, so that
+    # deblocking and SAO act at every tile border; one option set per set, so that all tiles share one SPS and PPS
+    ("a", 64, 64, 16, 4, 8, 34, []),                  # 2 x 2 -> 120 x 100
+    ("b", 64, 64, 64, 6, 8, 36, []),                  # 3 x 2 -> 192 x 128: one CTB per tile
+    ("c", 64, 32, 32, 3, 8, 33, []),                  # 1 x 3 and 3 x 1
+    ("d", 128, 128, 32, 4, 10, 32, ["--slices", "2"]),  # 2 x 2, Main10, two slices per tile picture
+    ("e", 256, 256, 64, 6, 8, 35, []),                # 3 x 2 -> 700 x 500: several K1 pool rows, cropped last row / column
+]
+
+
+def _ps_nals(stream):
+    """the SPS and PPS NAL units of an HEVC Annex-B stream"""
+    parts = stream.replace(b"\x00\x00\x00\x01", b"\x00\x00\x01").split(b"\x00\x00\x01")
+    return [p for p in parts if p and ((p[0] >> 1) & 63) in (33, 34)]
+
+
+def heif():
+    """tests/golden/heif/: tile pictures for HEIF grids (named .hevc / .avc: they are tiles, not the pictures the
+    stream suites walk).  Each set is one crop of the source content cut into equal tiles, every tile encoded on its
+    own with the set's options; the SPS and PPS bytes must come out identical across the tiles of a set."""
+    out_dir = os.path.join(ROOT, "tests/golden/heif")
+    os.makedirs(out_dir, exist_ok=True)
+    planes = source_planes()
+    manifest = []
+    for name, tw, th, ctb, n, bd, qp, opts in HEIF_SETS:
+        cols = 3 if n in (3, 6) else 2
+        rows = n // cols
+        canvas = make_content(planes, cols * tw, rows * th, 700 + ord(name), 6, bd)  # (noise: residuals at QP >= 32)
+        ps = None
+        for t in range(n):
+            ty, tx = divmod(t, cols)
+            tile = [canvas[0][ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw]] + [
+                p[ty * th // 2:(ty + 1) * th // 2, tx * tw // 2:(tx + 1) * tw // 2] for p in canvas[1:]]
+            path = os.path.join(out_dir, f"{name}_{t}.hevc")
+            nb = encode(tile, tw, th, bd, qp, 7000 + 16 * ord(name) + t, path, ["--ctb", str(ctb), "--sao", "1"] + opts)
+            got = _ps_nals(open(path, "rb").read())
+            if ps is not None and got != ps:
+                raise SystemExit(f"{path}: SPS / PPS differ from tile 0's (seed-dependent parameter sets)")
+            ps = got
+            print(f"{path}: {nb} B", flush=True)
+            if name == "a" and t == 1:
+                # the same tile once more with a PPS-level option (pps_cb_qp_offset): its SPS must be the set's and
+                # only its PPS differ -- the vector for "tiles carry different PPS"
+                path = os.path.join(out_dir, "a_1_pps.hevc")
+                encode(tile, tw, th, bd, qp, 7000 + 16 * ord(name) + t, path, ["--ctb", str(ctb), "--sao", "1", "--cbqp", "2"] + opts)
+                odd = _ps_nals(open(path, "rb").read())
+                if [p for p in odd if (p[0] >> 1) & 63 == 33] != [p for p in ps if (p[0] >> 1) & 63 == 33] or odd == ps:
+                    raise SystemExit(f"{path}: --cbqp must change the PPS and leave the SPS alone")
+        manifest.append({"set": name, "tile_w": tw, "tile_h": th, "ctb": ctb, "tiles": n, "bit_depth": bd, "qp": qp, "options": opts})
+    canvas = make_content(planes, 128, 128, 790, 1, 8)
+    for t in range(4):  # H.264 tiles: a grid of them is rejected
+        ty, tx = divmod(t, 2)
+        tile = [canvas[0][ty * 64:(ty + 1) * 64, tx * 64:(tx + 1) * 64]] + [p[ty * 32:(ty + 1) * 32, tx * 32:(tx + 1) * 32] for p in canvas[1:]]
+        path = os.path.join(out_dir, f"h264_{t}.avc")
+        print(f"{path}: {encode(tile, 64, 64, 8, 32, 7900 + t, path, [], codec=264)} B", flush=True)
+    manifest.append({"set": "h264", "tile_w": 64, "tile_h": 64, "tiles": 4, "bit_depth": 8, "qp": 32, "options": []})
+    json.dump(manifest, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1)
+
+
 if __name__ == "__main__":
     build_gen()
     what = sys.argv[1] if len(sys.argv) > 1 else "bench"
     {"bench": bench, "parity": parity, "4k": fourk, "parity264": parity264, "bench264": bench264,
      "mixed": mixed, "f3": f3, "heavy": heavy, "malformed": malformed, "nosdh": nosdh, "entropy": entropy,
-     "wide264": wide264, "leftcrop": leftcrop, "heavy264": heavy264, "tall264": tall264, "aim": aim}[what]()
+     "wide264": wide264, "leftcrop": leftcrop, "heavy264": heavy264, "tall264": tall264, "aim": aim, "heif": heif}[what]()

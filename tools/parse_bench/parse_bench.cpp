@@ -16,6 +16,9 @@
 #include "bitstream.h"
 #include "cabac.h"
 #include "job.h"
+#ifdef H2J_HEIF_INPUT
+#include "heif.h"
+#endif
 #ifdef H2J_SAMPLE
 #include "sampler.h"
 #endif
@@ -271,8 +274,14 @@ int main(int argc, char** argv) {
         for (int i = next++; i < total; i = next++) {
             const auto& s = streams[i % streams.size()];
             const int codec = h2j::detect_codec(s.data(), s.size());
+#ifdef H2J_HEIF_INPUT  // built with heif.cpp and heif_parse.cpp: HEIF files parse as the engine parses them
+            const int rc = h2j::is_heif(s.data(), s.size()) ? h2j::heif_parse_picture(s.data(), s.size(), job)
+                           : codec == 265                   ? h2j::hevc_parse_picture(s.data(), s.size(), job)
+                                                            : h2j::h264_parse_picture(s.data(), s.size(), job);
+#else
             const int rc = codec == 265 ? h2j::hevc_parse_picture(s.data(), s.size(), job)
                                         : h2j::h264_parse_picture(s.data(), s.size(), job);
+#endif
             if (rc) {
                 std::fprintf(stderr, "parse error %d: %s\n", rc, job.message.c_str());
                 failed++;
