@@ -85,8 +85,9 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             const int src = source_of(o);
             for (size_t v = v0; v < p.scaled.size(); v++) {
                 const h2j_scaled& sv = p.scaled[v];
-                // (a raw output reads any view with its planes: the quantiser scale does not change them)
-                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && (p.vqscale[v] == o.qscale || o.format) && p.vsharpen[v] == o.sharpen &&
+                // (a raw output reads any view with its planes: the quantiser scale does not change them; so does the
+                // canvas of a padded output.  A canvas view has the source -1: it is nobody's picture)
+                if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && (p.vqscale[v] == o.qscale || o.format || o.pad) && p.vsharpen[v] == o.sharpen &&
                     (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
                     return static_cast<int>(v);
             }
@@ -98,11 +99,45 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             sc.jpeg_h = resample ? o.fit_h : h2j_scaled_dim((o.windowed || o.orient) ? o.win_h : f.out_h, sc.scale_log2);
             p.scaled.push_back(sc);
             p.vsrc.push_back(src);
-            p.vqscale.push_back(o.qscale);
+            p.vqscale.push_back(o.pad ? 0 : o.qscale);  // (a padded output's quantiser scale is its canvas's)
             p.vsharpen.push_back(o.sharpen);
+            p.qforced = p.qforced || (o.qscale != 0 && !o.pad);
+            p.vjpeg.push_back(0);
+            p.vpad.push_back(-1);
+            return static_cast<int>(p.scaled.size()) - 1;
+        };
+        auto canvas_of = [&](const FrameJob::Output& o) {  // the canvas view of a padded output, added if new
+            const int pv = view_of(o);
+            for (size_t i = 0; i < p.pads.size(); i++) {
+                const h2j_pad& rec = p.pads[i];
+                if (p.padsrc[i] == pv && rec.bw == o.box_w && rec.bh == o.box_h && rec.px == o.pad_x && rec.py == o.pad_y &&
+                    rec.fill[0] == o.fill[0] && rec.fill[1] == o.fill[1] && rec.fill[2] == o.fill[2] &&
+                    (p.vqscale[p.padview[i]] == o.qscale || o.format))
+                    return p.padview[i];
+            }
+            h2j_pad rec{};
+            rec.w = p.scaled[pv].jpeg_w;
+            rec.h = p.scaled[pv].jpeg_h;
+            rec.bw = o.box_w;
+            rec.bh = o.box_h;
+            rec.px = o.pad_x;
+            rec.py = o.pad_y;
+            for (int c = 0; c < 3; c++) rec.fill[c] = o.fill[c];
+            h2j_scaled sc{};
+            sc.frame = k;
+            sc.jpeg_w = o.box_w;
+            sc.jpeg_h = o.box_h;
+            p.scaled.push_back(sc);
+            p.vsrc.push_back(-1);
+            p.vqscale.push_back(o.qscale);
+            p.vsharpen.push_back(0);
             p.qforced = p.qforced || o.qscale != 0;
             p.vjpeg.push_back(0);
-            return static_cast<int>(p.scaled.size()) - 1;
+            p.vpad.push_back(static_cast<int>(p.pads.size()));
+            p.pads.push_back(rec);
+            p.padsrc.push_back(pv);
+            p.padview.push_back(static_cast<int>(p.scaled.size()) - 1);
+            return p.padview.back();
         };
         auto rgb_of = [&](int v, int layout) {  // the raw output of view v in this layout, added if new
             for (size_t i = 0; i < p.rgbs.size(); i++)
@@ -123,14 +158,18 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             }
         // with raw outputs among them the JPEG renditions name their views first, in their order, so that a raw
         // output finds the view of a JPEG rendition with its planes wherever the two stand in the list
+        // (likewise with padded outputs: the unpadded JPEG renditions name their views before a padded one looks for
+        // its picture part, then the padded JPEG renditions their canvases before a padded raw one looks for one)
         bool raw = false;
-        for (int r = 0; r < j.nouts; r++) raw = raw || (j.outs[r].error == 0 && j.outs[r].format);
+        for (int r = 0; r < j.nouts; r++) raw = raw || (j.outs[r].error == 0 && (j.outs[r].format || j.outs[r].pad));
         for (int r = 0; raw && r < j.nouts; r++)
-            if (j.outs[r].error == 0 && !j.outs[r].format) view_of(j.outs[r]);
+            if (j.outs[r].error == 0 && !j.outs[r].format && !j.outs[r].pad) view_of(j.outs[r]);
+        for (int r = 0; raw && r < j.nouts; r++)
+            if (j.outs[r].error == 0 && !j.outs[r].format && j.outs[r].pad) canvas_of(j.outs[r]);
         for (int r = 0; r < j.nouts; r++) {
             const FrameJob::Output& o = j.outs[r];
             if (o.error != 0) continue;
-            const int v = view_of(o);
+            const int v = o.pad ? canvas_of(o) : view_of(o);
             if (!o.format) p.vjpeg[v] = 1;
             p.rends.push_back(ChunkPlan::Rend{j.out_base + r, v, o.format ? rgb_of(v, o.format) : -1});
         }
@@ -160,7 +199,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     p.at.bytes = c.off;  // the maps follow (layout_maps)
 }
 
-// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][rgb][jcoef][res][aux]
+// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][bpic][rgb][jcoef][res][aux]
 void layout_arena(ChunkPlan& p) {
     Cursor a;
     for (h2j_frame& f : p.frames) {
@@ -239,6 +278,17 @@ void layout_arena(ChunkPlan& p) {
         rec.dst = a.take(po);
         p.vfin[v] = static_cast<int>(p.fins.size());
         p.fins.push_back(rec);
+    }
+    p.pad_bytes = 0;
+    for (h2j_pad& rec : p.pads) {  // the 8-bit canvas planes K3b writes and K4 / K3c read (padded outputs only)
+        size_t po = 0;
+        for (int c = 0; c < 3; c++) {
+            rec.dst_stride[c] = h2j_spic_stride(c ? rec.bw / 2 : rec.bw);
+            rec.dst_off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(rec.dst_stride[c]) * (c ? rec.bh / 2 : rec.bh);
+        }
+        rec.dst = a.take(po);
+        p.pad_bytes += po;
     }
     p.rgb_base = a.off;  // the RGB pixels K3c writes (raw outputs only): one region, each output 256-byte aligned
     for (h2j_rgb& rec : p.rgbs) rec.dst_off = a.take(3 * static_cast<size_t>(rec.w) * rec.h);
@@ -406,8 +456,8 @@ void build_scale_classes(ChunkPlan& p) {
     }
 }
 
-// the source half of a K3u or K3c record (the fields have the same names in both): the planes K3u / K3c read, as
-// the view `src` shows them; wide: the 8-bit planes a scale or finishing kernel wrote (aligned dword loads)
+// the source half of a K3u, K3b or K3c record (the fields have the same names in all three): the planes the stage reads,
+// as the view `src` shows them; wide: the 8-bit planes a scale or finishing kernel wrote (aligned dword loads)
 template <typename Rec>
 void fill_source(Rec& rec, const h2j_frame& src, bool wide) {
     rec.bit_depth = src.bit_depth;
@@ -421,7 +471,7 @@ void fill_source(Rec& rec, const h2j_frame& src, bool wide) {
         rec.src_off[c] = src.pic_off[c];
     }
 }
-// the class of a K3u or K3c record: 0: the 8-bit planes K3s / K3r / K3p (/ K3u) wrote; 1: another 8-bit source; 2: a
+// the class of a K3u, K3b or K3c record: 0: the 8-bit planes K3s / K3r / K3p (/ K3u) wrote; 1: another 8-bit source; 2: a
 // 16-bit source
 template <typename Rec>
 int source_class(const Rec& rec) { return rec.wide ? 0 : rec.bit_depth > 8 ? 2 : 1; }
@@ -441,10 +491,16 @@ void build_late_stage_maps(ChunkPlan& p) {
     for (int v = 0; v < p.nv; v++)
         if (p.vfin[v] >= 0) fill_source(p.fins[p.vfin[v]], p.base_view(v), p.scaled[v].scale_log2 != 0);
     p.finmap.group(p.fins, source_class<h2j_finish>, [](const h2j_finish& rec) { return h2j_k3u_tiles(rec.w, rec.h); });
-    // K3c: the raw outputs with their sources (what view() shows K4)
+    // K3b: the canvases with their sources (what view() shows K4 of the picture part)
+    for (size_t i = 0; i < p.pads.size(); i++) {
+        const int v = p.padsrc[i];
+        fill_source(p.pads[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0);
+    }
+    p.padmap.group(p.pads, source_class<h2j_pad>, [](const h2j_pad& rec) { return h2j_k3b_tiles(rec.bw, rec.bh); });
+    // K3c: the raw outputs with their sources (what view() shows K4; a canvas is wide)
     for (size_t i = 0; i < p.rgbs.size(); i++) {
         const int v = p.rgbview[i];
-        fill_source(p.rgbs[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0);
+        fill_source(p.rgbs[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0 || p.vpad[v] >= 0);
     }
     p.rgbmap.group(p.rgbs, source_class<h2j_rgb>, [](const h2j_rgb& rec) { return h2j_k3c_tiles(rec.w, rec.h); });
 }
@@ -474,6 +530,7 @@ void layout_maps(ChunkPlan& p) {
     p.rgbmap.at = c.take(p.rgbmap.staging_bytes());
     p.at.jcompact = c.off;  // only in chunks with views that get no JPEG: the views K4 / K5 run on
     if (p.compact()) c.take(static_cast<size_t>(p.njpeg) * sizeof(h2j_frame));
+    p.padmap.at = c.take(p.padmap.staging_bytes());  // behind everything else
     p.at.bytes = c.off;
 }
 
@@ -500,7 +557,8 @@ void fill_descriptor(ChunkPlan& p) {
     // (a window: always K4a, on the window; a sharpened view: always K4a, on the sharpened planes)
     for (int v = 0; v < p.nv; v++)
         if (p.vjpeg[v])  // (K4 runs on the views that get a JPEG)
-            d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v]) ? 0 : 1;
+            d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v] &&
+                             p.vpad[v] < 0) ? 0 : 1;  // (a canvas: always K4a, on the padded planes)
 }
 
 }  // namespace
@@ -510,20 +568,29 @@ void fill_descriptor(ChunkPlan& p) {
 // jcoef / tile region and jstat (the first view keeps the frame's own).
 // A sharpened view is the 8-bit picture K3u writes at its h2j_finish record's dst, from what the view is without
 // the sharpening (base_view)
+// A canvas view is the 8-bit picture K3b writes at its h2j_pad record's dst
 h2j_frame ChunkPlan::view(int v) const {
-    h2j_frame f = base_view(v);
+    // f with the w x h 8-bit planes a late stage wrote at dst for its picture (pic == pic2: K4a sums their MB variances)
+    auto shows = [](h2j_frame f, uint64_t dst, int w, int h, const int32_t* stride, const int32_t* off) {
+        f.pic = f.pic2 = dst;
+        f.crop_x = f.crop_y = 0;
+        f.out_w = w;
+        f.out_h = h;
+        f.bit_depth = f.bit_depth_c = 8;
+        for (int c = 0; c < 3; c++) {
+            f.pic_stride[c] = stride[c];
+            f.pic_off[c] = off[c];
+        }
+        return f;
+    };
+    const h2j_frame f = base_view(v);
+    if (vpad[v] >= 0) {
+        const h2j_pad& rec = pads[vpad[v]];
+        return shows(f, rec.dst, rec.bw, rec.bh, rec.dst_stride, rec.dst_off);
+    }
     if (vfin[v] < 0) return f;
     const h2j_finish& rec = fins[vfin[v]];
-    f.pic = f.pic2 = rec.dst;  // pic == pic2: K4a sums the sharpened picture's MB variances
-    f.crop_x = f.crop_y = 0;
-    f.out_w = rec.w;
-    f.out_h = rec.h;
-    f.bit_depth = f.bit_depth_c = 8;
-    for (int c = 0; c < 3; c++) {
-        f.pic_stride[c] = rec.dst_stride[c];
-        f.pic_off[c] = rec.dst_off[c];
-    }
-    return f;
+    return shows(f, rec.dst, rec.w, rec.h, rec.dst_stride, rec.dst_off);
 }
 
 h2j_frame ChunkPlan::base_view(int v) const {
@@ -591,7 +658,7 @@ void ChunkPlan::reset(int nframes) {
     vfirst.assign(static_cast<size_t>(nf) + 1, 0);
     fstat.assign(static_cast<size_t>(nf), 0);
     clear_all(k1map, k1map8, k1all, k1hevc, saomap, scaled, scalemap, pyrmap, vsrc, wins, rends, jviews);
-    clear_all(orients, orientmap, vqscale, vsharpen, fins, finmap, rgbs, rgbview, rgbmap, vjpeg);
+    clear_all(orients, orientmap, vqscale, vsharpen, fins, finmap, rgbs, rgbview, rgbmap, vjpeg, vpad, pads, padview, padsrc, padmap);
     qforced = false;
     px = 0;
     std::memset(&desc, 0, sizeof(desc));

@@ -20,7 +20,7 @@ constexpr size_t kSegBytesPerBlock = 272;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// The map of a late stage (K3o, K3u, K3c; include/h2j_gpu.h h2j_gpu_orient, h2j_gpu_finish, h2j_gpu_rgb): the stage's
+// The map of a late stage (K3o, K3u, K3b, K3c; include/h2j_gpu.h h2j_gpu_orient, h2j_gpu_finish, h2j_gpu_pad, h2j_gpu_rgb): the stage's
 // records grouped by class, uploaded behind the other maps, with each class's first record, count and the most
 // workgroups one record of the class needs -- one launch per class present.  A chunk without the stage has an empty
 // map, uploads nothing for it and does not launch it
@@ -129,7 +129,21 @@ struct ChunkPlan {
     std::vector<int> jviews;
     bool compact() const { return njpeg > 0 && njpeg < nv; }
 
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][rgb][jcoef][res][aux]
+    // Padded output (K3b): a padded rendition has two views.  The view of its picture part is a view like any other,
+    // found the way a raw output finds its view (the quantiser scale does not change the planes), so an unpadded
+    // rendition with the same (window, resolved output, sharpen) shares it and the scale stage and K3u run once; padded
+    // renditions alone never set its vjpeg.  The canvas view is what K4 / K5 or K3c read: a view of its own (vpad: its
+    // record; vsrc -1, scale_log2 0, no sharpening of its own; jpeg_w x jpeg_h the canvas) whose planes K3b writes into
+    // an arena region behind upic (bpic; the spic strides), which view() shows with pic == pic2.  Renditions with one
+    // picture view, one canvas size, one place, one fill colour -- and one quantiser scale, unless raw -- share a canvas
+    // view.  A chunk without padded outputs has none of this and uploads what it always did
+    std::vector<int> vpad;         // per view: -1, or its record in pads (a canvas view)
+    std::vector<h2j_pad> pads;     // the chunk's canvases, view-major
+    std::vector<int> padview, padsrc;  // per canvas: its view, the view of its picture part
+    StageMap<h2j_pad, H2J_PAD_CLASSES> padmap;  // the same grouped by source class
+    size_t pad_bytes = 0;          // the canvas bytes K3b writes (their planes' rows with the row padding)
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][bpic][rgb][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
     size_t seg_cap = 0;  // payload pool bytes (K5)
     int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)

@@ -28,13 +28,15 @@
 
 // The kernel library's optional late stages, null when the library in use is older than them (weak references:
 // bound when this library loads, so a stand-in or an older build selected beside it still loads): K3o; K3u and the
-// K4 entry that takes the quantiser scale from the caller; K3c
+// K4 entry that takes the quantiser scale from the caller; K3c; K3b
 extern "C" int h2j_gpu_orient(const h2j_gpu_batch*, const h2j_orient*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 extern "C" int h2j_gpu_finish(const h2j_gpu_batch*, const h2j_finish*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 extern "C" int h2j_gpu_jpeg2(const h2j_gpu_batch*, const int32_t*, void*) __attribute__((weak));
 extern "C" int h2j_gpu_rgb(const h2j_gpu_batch*, const h2j_rgb*, const int32_t*, const int32_t*, const int32_t*, void*)
+    __attribute__((weak));
+extern "C" int h2j_gpu_pad(const h2j_gpu_batch*, const h2j_pad*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 
 namespace h2j {
@@ -70,7 +72,7 @@ struct OptionalStage {
     const char* missing;
     int (*launch)(Engine&, Slot&);
 };
-enum { STAGE_ORIENT, STAGE_FINISH, STAGE_RGB };
+enum { STAGE_ORIENT, STAGE_FINISH, STAGE_RGB, STAGE_PAD };
 const OptionalStage kStages[] = {
     {[] { return h2j_gpu_orient != nullptr; }, [](const FrameJob::Output& o) { return o.orient != 0; },
      "the kernel library has no orientation stage (h2j_gpu_orient): oriented output needs a newer libh2j_hip.so",
@@ -81,6 +83,9 @@ const OptionalStage kStages[] = {
     {[] { return h2j_gpu_rgb != nullptr; }, [](const FrameJob::Output& o) { return o.format != 0; },
      "the kernel library has no RGB stage (h2j_gpu_rgb): raw output needs a newer libh2j_hip.so",
      [](Engine& e, Slot& s) { return e.late_stage(s, s.plan.rgbmap, h2j_gpu_rgb, kStages[STAGE_RGB].missing); }},
+    {[] { return h2j_gpu_pad != nullptr; }, [](const FrameJob::Output& o) { return o.pad != 0; },
+     "the kernel library has no padding stage (h2j_gpu_pad): padded output needs a newer libh2j_hip.so",
+     [](Engine& e, Slot& s) { return e.late_stage(s, s.plan.padmap, h2j_gpu_pad, kStages[STAGE_PAD].missing); }},
 };
 
 const char* no_stage_message(const FrameJob::Output& o) {
@@ -88,7 +93,7 @@ const char* no_stage_message(const FrameJob::Output& o) {
         if (st.needed(o) && !st.present()) return st.missing;
     return kStages[STAGE_RGB].missing;  // (asked of an output that lacks no stage: the last one's, as it always was)
 }
-void resolve_outputs(const h2j_out_opts6* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts7* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
@@ -100,7 +105,7 @@ void resolve_outputs(const h2j_out_opts6* o, int nr, FrameJob& job) {
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-static int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts6* o, int nr, FrameJob& job, bool* ran) {
+static int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts7* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -152,6 +157,7 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
     put(p.orientmap.at, p.orientmap.map.data(), p.orientmap.bytes());  // the late stages' maps: nothing in chunks without
     put(p.finmap.at, p.finmap.map.data(), p.finmap.bytes());
     put(p.rgbmap.at, p.rgbmap.map.data(), p.rgbmap.bytes());
+    put(p.padmap.at, p.padmap.map.data(), p.padmap.bytes());
     if (p.qforced && !p.compact()) put(p.at.qforce, p.vqscale.data(), static_cast<size_t>(p.nv) * 4);
     if (p.compact()) {  // the views K4 / K5 run on, and their forced scales, packed
         h2j_frame* jc = reinterpret_cast<h2j_frame*>(hin + p.at.jcompact);
@@ -247,10 +253,11 @@ int Engine::launch(Slot& s, const Slot* after) {
     if (s.stages >= 3 && h2j_gpu_sao(&b, st)) return drain_fail(s, h2j_gpu_last_error());
     h2j_gpu_event_record(s.ev[EV_K3], st);
     // the late stages run only in chunks with records for them (which exist only when the kernel library has the stage):
-    // K3o in front of the scale stage, K3u and K3c (out of place: K4 reads what it read) behind it
+    // K3o in front of the scale stage, K3u, K3b and K3c (out of place: K4 reads what it read, or the canvas K3b made)
+    // behind it
     if (kStages[STAGE_ORIENT].launch(*this, s)) return -1;
     if (s.stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
-    if (kStages[STAGE_FINISH].launch(*this, s) || kStages[STAGE_RGB].launch(*this, s)) return -1;
+    if (kStages[STAGE_FINISH].launch(*this, s) || kStages[STAGE_PAD].launch(*this, s) || kStages[STAGE_RGB].launch(*this, s)) return -1;
     h2j_gpu_event_record(s.ev[EV_SCALE], st);
     // a chunk of raw renditions only: nobody asked for a JPEG, so no K4 / K5 and no payload (the pool's byte count,
     // which K5 would have written, is cleared instead)
@@ -329,6 +336,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     double bytes = 0;
     for (const h2j_frame& f : s.plan.frames) bytes += 1.5 * f.out_w * f.out_h * (4.0 + (f.bit_depth > 8 ? 2.0 : 1.0));
     stats[ST_BYTES] += bytes;
+    if (s.stages >= 3) stats[ST_PAD_BYTES] += static_cast<double>(s.plan.pad_bytes);
     return 0;
 }
 
@@ -474,11 +482,19 @@ static double hbm_estimate(const FrameJob& j) {
     // raw outputs: the pixels K3c writes (3 B per output sample; one that shares a JPEG rendition's view added that
     // view's regions above for nothing: an overestimate)
     for (int r = 0; r < j.nouts; r++)
-        if (j.outs[r].error == 0 && j.outs[r].format) est += 3.0 * j.outs[r].out_w() * j.outs[r].out_h() + 4096;
+        if (j.outs[r].error == 0 && j.outs[r].format) est += 3.0 * j.outs[r].canvas_w() * j.outs[r].canvas_h() + 4096;
+    // padded outputs: the canvas is one more view -- its 8-bit planes, jcoef / tile region and share of the payload
+    // pool, from the canvas size (one that shares a canvas with another rendition: an overestimate)
+    for (int r = 0; r < j.nouts; r++)
+        if (j.outs[r].error == 0 && j.outs[r].pad) est += 14.5 * j.outs[r].box_w * j.outs[r].box_h + 8192;
     return est;
 }
-// JPEG outputs of a job (at least one: the chunk bound counts a failed item as one)
-static int views_estimate(const FrameJob& j) { return std::max(1, j.nouts); }
+// JPEG outputs of a job (at least one: the chunk bound counts a failed item as one; a padded output is two views)
+static int views_estimate(const FrameJob& j) {
+    int n = j.nouts;
+    for (int r = 0; r < j.nouts; r++) n += (j.outs[r].error == 0 && j.outs[r].pad) ? 1 : 0;
+    return std::max(1, n);
+}
 
 void Engine::start_threads() {
     std::lock_guard<std::mutex> g(amu);
@@ -715,13 +731,13 @@ int Engine::run_batch(Batch& b) {
                     }
                     FrameJob::Output& jo = jobs[k].outs[o - b.rbase[k]];
                     if (b.out_wh && jo.error != H2J_ERR_OUT_OPTS) {  // the options resolved: the output's size
-                        b.out_wh[2 * o] = jo.out_w();
-                        b.out_wh[2 * o + 1] = jo.out_h();
+                        b.out_wh[2 * o] = jo.canvas_w();
+                        b.out_wh[2 * o + 1] = jo.canvas_h();
                     }
                     // a raw rendition's size is known here: one that cannot fit the output buffer behind the raw
                     // renditions planned before it (JPEGs only take more) fails now, and K3c does not run for it
                     if (jo.error == 0 && jo.format) {
-                        const size_t len = 3 * static_cast<size_t>(jo.out_w()) * jo.out_h();
+                        const size_t len = 3 * static_cast<size_t>(jo.canvas_w()) * jo.canvas_h();
                         if (b.raw_planned + len > b.out_cap) {
                             jo.error = -50;
                             rc = -3;

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "api_ext.h"
 #include "bitstream.h"
 #include "engine.h"
 #include "heif.h"
@@ -19,7 +20,7 @@ struct h2j_engine {
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts6* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            const h2j_out_opts7* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                             int* status, bool latency, int32_t* out_wh = nullptr) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
@@ -36,7 +37,7 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + (nrend ? nrend[i] : 1);
     b->nout = b->rbase[n];
     if (opts) b->opts.assign(opts, opts + b->nout);
-    else b->opts.assign(static_cast<size_t>(b->nout), h2j::kPlainOutput);
+    else b->opts.assign(static_cast<size_t>(b->nout), h2j::kPlainOutput7);
     for (int i = 0; i < b->nout; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
@@ -80,12 +81,12 @@ static int64_t submit_multi_any(h2j_engine* w, int n, const uint8_t* const* data
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
     int total = 0;
     for (int i = 0; i < n; i++) total += nrend[i];
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::to_opts6(total, opts).data(), out, out_cap, out_off, out_len, status, latency, out_wh);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::to_opts7(total, opts).data(), out, out_cap, out_off, out_len, status, latency, out_wh);
     return latency ? h2j_engine_wait(w, t) : t;
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts6* o = &h2j::kPlainOutput, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts7* o = &h2j::kPlainOutput7, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -132,8 +133,9 @@ static int copy_planes(Engine& e, Slot& s, int k, int stage, uint16_t* planes_ou
 
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
-// (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too; 12: qscale and sharpen too)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts6* o, int nrend, int pick,
+// (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too; 12: qscale and sharpen too; 18: the
+// padding too)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts7* o, int nrend, int pick,
                               uint8_t* planes_out, size_t cap, int* info, int info_n = 4) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
@@ -157,12 +159,14 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
     // the picture K4 would read: the JPEG source view of the rendition
     const h2j_frame& f = s.plan.frames[0];
     const int vi = s.plan.rends[static_cast<size_t>(pick)].view;
-    const h2j_scaled& sc = s.plan.scaled[vi];
+    // (a padded rendition's view is its canvas; the mode is that of the view of its picture part)
+    const bool padded = s.plan.vpad[vi] >= 0;
+    const h2j_scaled& sc = s.plan.scaled[padded ? s.plan.padsrc[s.plan.vpad[vi]] : vi];
     const h2j_frame v = s.plan.view(vi);
     const int w_ = v.out_w, h_ = v.out_h;
     int levels = 0;  // K3s levels among the views of the same window: two or more are K3p's
     for (int x = 0; x < s.plan.nv; x++)
-        if (s.plan.scaled[x].scale_log2 >= 1 && s.plan.scaled[x].scale_log2 <= 3 && s.plan.vsrc[x] == s.plan.vsrc[vi])
+        if (s.plan.scaled[x].scale_log2 >= 1 && s.plan.scaled[x].scale_log2 <= 3 && s.plan.vsrc[x] == s.plan.vsrc[padded ? s.plan.padsrc[s.plan.vpad[vi]] : vi])
             levels |= 1 << s.plan.scaled[x].scale_log2;
     info[0] = w_;
     info[1] = h_;
@@ -186,12 +190,20 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
         info[10] = st.qscale;
         info[11] = wo.sharpen;
     }
+    if (info_n >= 18) {
+        info[12] = wo.pad;
+        info[13] = wo.pad_x;
+        info[14] = wo.pad_y;
+        info[15] = wo.out_w();
+        info[16] = wo.out_h();
+        info[17] = wo.fill[0] | (wo.fill[1] << 8) | (wo.fill[2] << 16);
+    }
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
     size_t bytes = 0;  // the view's planes in the arena, from v.pic2
     for (int c = 0; c < 3; c++) {
         // (an unscaled oriented view lies in the oriented planes, whose rows end with the oriented picture's)
-        const int rows = (sc.scale_log2 || wo.sharpen) ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
+        const int rows = (sc.scale_log2 || wo.sharpen || padded) ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
         bytes = std::max(bytes, (static_cast<size_t>(v.pic_off[c]) + static_cast<size_t>(v.pic_stride[c]) * rows) * pel);
     }
     std::vector<uint8_t> tmp(bytes);
@@ -219,8 +231,20 @@ static int decode_multi_any(h2j_engine* w, const uint8_t* data, size_t size, int
                             size_t cap, int* info, int info_n) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::to_opts6(nrend, opts).data(), nrend, pick, planes_out, cap, info, info_n);
+    return decode_jpeg_source(w, data, size, h2j::to_opts7(nrend, opts).data(), nrend, pick, planes_out, cap, info, info_n);
 }
+
+// the engine calls of libH265ToJpegExt.so (api_ext.h): the multi6 calls with h2j_out_opts7
+namespace h2j {
+int64_t submit_multi7(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend, const h2j_out_opts7* opts,
+                      uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len, int* status, int32_t* out_wh, bool latency) {
+    return submit_multi_any(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, latency, out_wh);
+}
+int decode_multi7(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts7* opts, int pick, uint8_t* planes_out,
+                  size_t cap, int* info) {
+    return decode_multi_any(w, data, size, nrend, opts, pick, planes_out, cap, info, 18);
+}
+}  // namespace h2j
 
 extern "C" {
 
@@ -279,14 +303,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts6(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts6(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -319,7 +343,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts6(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -327,7 +351,7 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts6(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -417,7 +441,7 @@ int h2j_engine_decode_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     e.par(n, [&](int i) {
         e.jobs[i].threads = 1;
         rc[i] = h2j::parse_any(data[i], sizes[i], e.jobs[i]);
-        if (rc[i] == 0) h2j::resolve_outputs(&h2j::kPlainOutput, 1, e.jobs[i]);
+        if (rc[i] == 0) h2j::resolve_outputs(&h2j::kPlainOutput7, 1, e.jobs[i]);
     });
     for (int i = 0; i < n; i++)
         if (rc[i]) {
@@ -457,13 +481,13 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts6 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
+    const h2j_out_opts7 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts6 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, 0, {0, 0, 0}};
+    const h2j_out_opts7 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 

@@ -52,9 +52,18 @@ struct FrameJob {
         // RGB output (include/h2j.h "RGB output"): 0 the JPEG; H2J_FMT_RGB8 / H2J_FMT_RGB8_PLANAR: the output's final
         // 8-bit planes as RGB pixels, made by K3c
         int format = 0;
-        // the output's luma size: the window's at the resolved scale, or the fit size
+        // padded output (include/h2j.h "Padded output"): pad 1: K3b writes the output's final 8-bit planes into a
+        // canvas of box_w x box_h at (pad_x, pad_y), the rest the fill bytes (Y, Cb, Cr); an output with nothing to pad
+        // has pad 0: it is the one without the option
+        int pad = 0, box_w = 0, box_h = 0, pad_x = 0, pad_y = 0;
+        uint8_t fill[3] = {0, 0, 0};
+        // the luma size of the output's picture part (all of it without pad; the scale stage sizes from it): the
+        // window's at the resolved scale, or the fit size
         int out_w() const { return scale_log2 == H2J_SCALE_RESAMPLE ? fit_w : h2j_scaled_dim(win_w, scale_log2); }
         int out_h() const { return scale_log2 == H2J_SCALE_RESAMPLE ? fit_h : h2j_scaled_dim(win_h, scale_log2); }
+        // the luma size of what the caller gets (SOF0, out_wh, raw sizes): the canvas of a padded output
+        int canvas_w() const { return pad ? box_w : out_w(); }
+        int canvas_h() const { return pad ? box_h : out_h(); }
     };
     Output outs[H2J_MAX_RENDITIONS];
     int nouts = 0;

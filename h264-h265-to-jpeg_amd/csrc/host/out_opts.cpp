@@ -24,13 +24,28 @@ h2j_out_opts6 to_opts6(const h2j_out_opts5& o) {
                          o.qscale, o.sharpen, 0, {o.reserved[0] | o.reserved[1], o.reserved[2], o.reserved[3]}};
 }
 
+const h2j_out_opts7 kPlainOutput7 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
+// (pad and background took over reserved[0..1] of h2j_out_opts6)
+h2j_out_opts7 widen7(const h2j_out_opts6& o) {
+    return h2j_out_opts7{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
+                         o.qscale, o.sharpen, o.format, 0, 0, {o.reserved[0] | o.reserved[1] | o.reserved[2]}};
+}
+
 bool reserved_zero(const h2j_out_opts6& o) { return std::all_of(o.reserved, o.reserved + 3, [](int32_t r) { return r == 0; }); }
+bool reserved_zero(const h2j_out_opts7& o) { return o.reserved[0] == 0; }
+// padded output (include/h2j.h "Padded output"): a two-sided box to pad to, a 24-bit colour, and no colour without pad
+bool pad_valid(const h2j_out_opts7& o) {
+    if (o.pad < 0 || o.pad > 1 || (o.background & ~0xFFFFFF)) return false;
+    if (!o.pad) return o.background == 0;
+    // (the canvas is the caller's number, not the picture's: H2J_PAD_MAX_SAMPLES bounds its memory and its int32 offsets)
+    return o.fit_w >= 2 && o.fit_h >= 2 && static_cast<int64_t>(2 * (o.fit_w / 2)) * (2 * (o.fit_h / 2)) <= H2J_PAD_MAX_SAMPLES;
+}
 // finishing (include/h2j.h "Finishing"): a fixed quantiser scale, an unsharp mask
-bool finish_valid(const h2j_out_opts6& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
+bool finish_valid(const h2j_out_opts7& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
 // RGB output (include/h2j.h "RGB output"): a known format, and no quantiser scale for pixels
-bool format_valid(const h2j_out_opts6& o) { return o.format >= H2J_FMT_JPEG && o.format <= H2J_FMT_RGB8_PLANAR && !(o.format && o.qscale); }
+bool format_valid(const h2j_out_opts7& o) { return o.format >= H2J_FMT_JPEG && o.format <= H2J_FMT_RGB8_PLANAR && !(o.format && o.qscale); }
 // the orientation (0, 2..8) the options name for a picture whose display orientation SEI says sei_orient
-int resolve_orient(const h2j_out_opts6& o, int sei_orient) {
+int resolve_orient(const h2j_out_opts7& o, int sei_orient) {
     const int r = o.orient == H2J_ORIENT_AUTO ? sei_orient : o.orient;
     return r == 1 ? 0 : r;
 }
@@ -43,9 +58,9 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
 }
 // what can be said of the options before the picture's size is known (an item none of whose renditions
 // passes is not parsed); the window's place in the picture is checked by resolve_output
-bool out_opts_valid(const h2j_out_opts6& o) {
+bool out_opts_valid(const h2j_out_opts7& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o) || !format_valid(o)) return false;
+    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o) || !format_valid(o) || !pad_valid(o)) return false;
     if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
     if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
         if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
@@ -54,7 +69,7 @@ bool out_opts_valid(const h2j_out_opts6& o) {
     if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts6& o, int w, int h) {
+int resolve_scale(const h2j_out_opts7& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
@@ -67,7 +82,7 @@ int resolve_scale(const h2j_out_opts6& o, int w, int h) {
 // resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest.
 // Orientation (include/h2j.h "Orientation"; sei_orient: the picture's, for H2J_ORIENT_AUTO) comes first: the
 // rule runs on the oriented size, the window is in the oriented picture
-FrameJob::Output resolve_output(const h2j_out_opts6& o, int W, int H, int sei_orient) {
+static FrameJob::Output resolve_picture(const h2j_out_opts7& o, int W, int H, int sei_orient) {
     FrameJob::Output out;
     out.qscale = o.qscale;
     out.sharpen = o.sharpen;
@@ -110,9 +125,36 @@ FrameJob::Output resolve_output(const h2j_out_opts6& o, int W, int H, int sei_or
     out.fit_h = oh;
     return out;
 }
+// ... and the padding (include/h2j.h "Padded output") last: the picture part is what the options without pad resolve
+// to, centred in the canvas the way cover centres its window; a picture part that fills the canvas is not padded
+FrameJob::Output resolve_output(const h2j_out_opts7& o, int W, int H, int sei_orient) {
+    FrameJob::Output out = resolve_picture(o, W, H, sei_orient);
+    if (out.error || !o.pad) return out;
+    const int bw = 2 * (o.fit_w / 2), bh = 2 * (o.fit_h / 2), ow = out.out_w(), oh = out.out_h();
+    if (ow == bw && oh == bh) return out;
+    int ycc[3] = {0, 128, 128};
+    pad_colour(static_cast<uint32_t>(o.background), ycc);
+    out.pad = 1;
+    out.box_w = bw;
+    out.box_h = bh;
+    out.pad_x = 2 * ((bw - ow) / 4);
+    out.pad_y = 2 * ((bh - oh) / 4);
+    for (int c = 0; c < 3; c++) out.fill[c] = static_cast<uint8_t>(ycc[c]);
+    return out;
+}
+int pad_colour(uint32_t rgb, int* ycc) {
+    if (!ycc || (rgb & ~0xFFFFFFu)) return H2J_ERR_OUT_OPTS;
+    const int r = static_cast<int>(rgb >> 16), g = static_cast<int>((rgb >> 8) & 255), b = static_cast<int>(rgb & 255);
+    auto clip = [](int v) { return v < 0 ? 0 : v > 255 ? 255 : v; };
+    // JFIF's forward matrix in 16.16 (libjpeg's jccolor.c constants; >> of a negative int is arithmetic here)
+    ycc[0] = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    ycc[1] = clip(((-11059 * r - 21709 * g + 32768 * b + 32768) >> 16) + 128);
+    ycc[2] = clip(((32768 * r - 27439 * g - 5329 * b + 32768) >> 16) + 128);
+    return 0;
+}
 // W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
 // message they always got
-std::string out_opts_message(const h2j_out_opts6& o, int W, int H, int sei_orient) {
+std::string out_opts_message(const h2j_out_opts7& o, int W, int H, int sei_orient) {
     std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
@@ -125,6 +167,9 @@ std::string out_opts_message(const h2j_out_opts6& o, int W, int H, int sei_orien
     if (o.qscale != 0 || o.sharpen != 0)
         m += "; qscale " + std::to_string(o.qscale) + " (0 or 2..31), sharpen " + std::to_string(o.sharpen) + " (0..64)";
     if (o.format != 0) m += "; format " + std::to_string(o.format) + " (0 JPEG, 1 RGB, 2 planar RGB; not with qscale)";
+    if (o.pad != 0 || o.background != 0)
+        m += "; pad " + std::to_string(o.pad) + " (0..1; needs a box: fit or cover with both sides, of at most " + std::to_string(H2J_PAD_MAX_SAMPLES) + " samples), background " + std::to_string(o.background) +
+             " (0x00RRGGBB, 0 without pad)";
     if (!(window && W > 0 && H > 0)) return m;
     const int ro = (o.orient >= H2J_ORIENT_AUTO && o.orient <= 8) ? resolve_orient(o, sei_orient) : 0;
     if (ro >= 5) std::swap(W, H);
@@ -134,7 +179,14 @@ std::string out_opts_message(const h2j_out_opts6& o, int W, int H, int sei_orien
 }
 
 int crop_window6(int w, int h, const h2j_out_opts6* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
-    if (!o || !win || !ow || !oh || !orient || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
+    if (!o) return H2J_ERR_OUT_OPTS;
+    const h2j_out_opts7 o7 = widen7(*o);  // (pad 0: the canvas is the picture part)
+    int32_t place[4];
+    return crop_window7(w, h, &o7, sei_orient, win, ow, oh, orient, place);
+}
+
+int crop_window7(int w, int h, const h2j_out_opts7* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient, int32_t* place) {
+    if (!o || !win || !ow || !oh || !orient || !place || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
         sei_orient > 8 || !out_opts_valid(*o))
         return H2J_ERR_OUT_OPTS;
     const FrameJob::Output out = resolve_output(*o, w, h, sei_orient == 1 ? 0 : sei_orient);
@@ -144,8 +196,12 @@ int crop_window6(int w, int h, const h2j_out_opts6* o, int sei_orient, int32_t* 
     win[1] = out.win_y;
     win[2] = out.win_w;
     win[3] = out.win_h;
-    *ow = out.out_w();
-    *oh = out.out_h();
+    *ow = out.canvas_w();
+    *oh = out.canvas_h();
+    place[0] = out.pad_x;
+    place[1] = out.pad_y;
+    place[2] = out.out_w();
+    place[3] = out.out_h();
     return 0;
 }
 

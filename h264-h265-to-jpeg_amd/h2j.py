@@ -16,6 +16,10 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libH265ToJpeg.so"
+# the C entry points younger than libH265ToJpeg.so's fixed export list (csrc/host/api_ext.h): a thin library beside it
+_EXT_LIB_NAME = "libH265ToJpegExt.so"
+_EXT_SYMBOLS = ("h2j_engine_transcode_multi7", "h2j_engine_submit_multi7", "h2j_engine_decode_multi7",
+                "h2j_h265_to_jpeg_mem_multi7", "h2j_crop_window7", "h2j_pad_colour")
 _lib = None
 
 
@@ -63,6 +67,16 @@ class OutOpts6(ctypes.Structure):
                 ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
                 ("orient", ctypes.c_int32), ("qscale", ctypes.c_int32), ("sharpen", ctypes.c_int32),
                 ("format", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class OutOpts7(ctypes.Structure):
+    """include/h2j.h h2j_out_opts7: h2j_out_opts6 and the padding (letterbox to the box, the fill colour 0x00RRGGBB)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("orient", ctypes.c_int32), ("qscale", ctypes.c_int32), ("sharpen", ctypes.c_int32),
+                ("format", ctypes.c_int32), ("pad", ctypes.c_int32), ("background", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 1)]
 
 
 FMT_JPEG, FMT_RGB8, FMT_RGB8_PLANAR = 0, 1, 2  # include/h2j.h H2J_FMT_*
@@ -232,6 +246,33 @@ def load_library() -> ctypes.CDLL:
         lib.h2j_crop_window6.restype = ctypes.c_int
         lib.h2j_crop_window6.argtypes = [ctypes.c_int, ctypes.c_int, opt6p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    # padded output: its entry points live in libH265ToJpegExt.so, in the directory the host library came from (an
+    # older build selected through H2J_LIB_DIR has none: it still loads, and a padded call on it fails with
+    # AttributeError); they are bound as attributes of `lib`, so callers find every entry point in one place
+    ext_path = os.path.join(os.path.dirname(path), _EXT_LIB_NAME)
+    if os.path.exists(ext_path):
+        ext = ctypes.CDLL(ext_path, mode=ctypes.RTLD_GLOBAL)
+        for sym in _EXT_SYMBOLS:
+            setattr(lib, sym, getattr(ext, sym))
+    if hasattr(lib, "h2j_engine_transcode_multi7"):
+        opt7p = ctypes.POINTER(OutOpts7)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi7.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi7.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt7p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_engine_submit_multi7.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi7.argtypes = lib.h2j_engine_transcode_multi7.argtypes
+        lib.h2j_engine_decode_multi7.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi7.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt7p, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi7.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi7.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt7p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_crop_window7.restype = ctypes.c_int
+        lib.h2j_crop_window7.argtypes = [ctypes.c_int, ctypes.c_int, opt7p, ctypes.c_int, i32p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_pad_colour.restype = ctypes.c_int
+        lib.h2j_pad_colour.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -263,6 +304,8 @@ STAT_KEYS = ["parse_ms", "h2d_ms", "recon_ms", "deblock_ms", "sao_ms", "jpeg_ms"
              "assemble_ms", "total_ms", "frames", "alg_bytes", "entropy_ms", "prep_ms", "chunks", "pack_ms",
              "parse_run_ms", "d2h_stats_ms", "d2h_payload_ms", "payload_bytes", "host_grow_ms", "h2d_bytes",
              "payload_copied_bytes", "scale_ms", "renditions", "parsed", "raw_bytes"]
+# the entries of h2j_engine_stats behind those (a kernel or host library older than them leaves them 0)
+STAT_KEYS_LATER = ["pad_bytes"]
 
 
 def _per_item(v, n, name):
@@ -319,7 +362,26 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen", "format")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen", "format", "pad")
+
+
+def _is_colour(v):
+    """An (r, g, b) colour: a tuple or list of three ints (no entry of a per-item or per-batch sequence is an int, so a
+    sequence of three ints is never one of those)."""
+    return (isinstance(v, (tuple, list)) and len(v) == 3 and
+            all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in v))
+
+
+def _pad_value(v, what):
+    """A padding as h2j_out_opts7 takes it, (pad, background): None or False: (0, 0); True: black; (r, g, b), each
+    0..255: that colour as 0x00RRGGBB."""
+    if v is None or v is False:
+        return (0, 0)
+    if v is True:
+        return (1, 0)
+    if _is_colour(v) and all(0 <= x <= 255 for x in v):
+        return (1, (int(v[0]) << 16) | (int(v[1]) << 8) | int(v[2]))
+    raise ValueError(f"{what}: pad {v!r} is not True or an (r, g, b) colour with each value 0..255")
 
 
 def _format_value(v, what):
@@ -360,7 +422,8 @@ def rendition_spec(spec):
     a crop or cover key (crop_x, crop_y, crop_w, crop_h) follow: the fields of h2j_out_opts3; with an orient
     key those and orient: the fields of h2j_out_opts4; with a qscale or sharpen key those (orient 0 if the spec
     names none), qscale and sharpen: the fields of h2j_out_opts5; with a format key those (0 where the spec names
-    none) and format: the fields of h2j_out_opts6.
+    none) and format: the fields of h2j_out_opts6; with a pad key those (0 where the spec names none), pad and
+    background: the fields of h2j_out_opts7.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
     of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
@@ -370,7 +433,9 @@ def rendition_spec(spec):
     picture), qscale (2..31: the JPEG quantiser scale instead of the rate control's; 0: the rate control's) and
     sharpen (1..64: an unsharp mask of strength sharpen / 16 on the luma of the rendition's final 8-bit planes;
     0: none) and format ("jpeg": the file, as without the key; "rgb": the rendition's final picture as 8-bit RGB
-    pixels, numpy (H, W, 3); "rgb_planar": the same as (3, H, W) -- converted on the GPU, no JPEG loss).
+    pixels, numpy (H, W, 3); "rgb_planar": the same as (3, H, W) -- converted on the GPU, no JPEG loss) and pad (True,
+    or an (r, g, b) colour: the rendition letterboxed to the exact size of its box -- a two-sided fit, or a cover -- the
+    picture part centred, the rest black or that colour; the rendition then has the box's size whatever the picture's).
     Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
@@ -382,7 +447,11 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad)")
+        if "pad" in spec:  # the h2j_out_opts7 fields, whatever else the spec names
+            rest = dict(spec)
+            pad = _pad_value(rest.pop("pad"), f"rendition {spec!r}")
+            return (tuple(rendition_spec(rest)) + (0,) * 8)[:13] + pad
         if "format" in spec:  # the h2j_out_opts6 fields, whatever else the spec names
             rest = dict(spec)
             fmt = _format_value(rest.pop("format"), f"rendition {spec!r}")
@@ -472,7 +541,9 @@ def _multi_opts(per_item):
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    if any(len(t) > 12 for t in flat):  # a format: the multi6 calls
+    if any(len(t) > 13 for t in flat):  # a padding: the multi7 calls
+        opts = (OutOpts7 * len(flat))(*[OutOpts7(*(tuple(t) + (0,) * 10)[:15]) for t in flat])
+    elif any(len(t) > 12 for t in flat):  # a format: the multi6 calls
         opts = (OutOpts6 * len(flat))(*[OutOpts6(*(tuple(t) + (0,) * 8)[:13]) for t in flat])
     elif any(len(t) > 10 for t in flat):  # a finishing option: the multi5 calls
         opts = (OutOpts5 * len(flat))(*[OutOpts5(*(tuple(t) + (0,) * 7)[:12]) for t in flat])
@@ -534,8 +605,18 @@ def _per_item_format(v, n):
     return v
 
 
-def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None, format=None):
-    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale, sharpen or format is given."""
+def _per_item_pad(v, n):
+    """pad (None, True / False or one (r, g, b) colour for every item, or a per-item sequence of those) -> n values."""
+    if v is None or isinstance(v, (bool, np.bool_)) or _is_colour(v):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"pad: {len(v)} entries for {n} streams")
+    return v
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None, format=None, pad=None):
+    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale, sharpen, format or pad is given."""
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
     ft = [None] * n if fit is None else _per_item_fit(fit, n)
     if isinstance(stretch, (bool, np.bool_)) or stretch is None:
@@ -549,6 +630,7 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
     orr = _per_item_orient(orient, n)
     qs, sh = _per_item_finish(qscale, n, "qscale"), _per_item_finish(sharpen, n, "sharpen")
     fm = _per_item_format(format, n)
+    pd = _per_item_pad(pad, n)
     out = []
     for i in range(n):
         d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
@@ -566,6 +648,8 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
             d["sharpen"] = sh[i]
         if fm[i] is not None:
             d["format"] = fm[i]
+        if pd[i] is not None and pd[i] is not False:
+            d["pad"] = pd[i]
         out.append([d])
     return out
 
@@ -663,7 +747,7 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None, pad=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -690,12 +774,16 @@ class Engine:
         or a per-item sequence of ints or None.
 
         format ("jpeg", "rgb", "rgb_planar"; h2j_out_opts6): one name for every item or a per-item sequence of names
-        or None; the entry of a raw item is a numpy uint8 array, (H, W, 3) or (3, H, W), instead of bytes."""
+        or None; the entry of a raw item is a numpy uint8 array, (H, W, 3) or (3, H, W), instead of bytes.
+
+        pad (True: black, or an (r, g, b) tuple; h2j_out_opts7): one value for every item or a per-item sequence of
+        values or None; the item is letterboxed to the exact size of its box (a two-sided fit, or a cover), so
+        transcode(streams, fit=(224, 224), pad=True, format="rgb_planar") returns arrays of one shape, (3, 224, 224)."""
         n = len(streams)
         if n == 0:
             return []
-        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format)):  # one rendition per item through the multi3 .. multi6 call
-            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format))
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format, pad)):  # one rendition per item through the multi3 .. multi7 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad))
             self.last_status = [st[0] for st in self.last_status]
             return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
@@ -730,7 +818,7 @@ class Engine:
 
         renditions: one list of specs for every item, or one such list per item (normalize_renditions);
         a spec is an int (scale), a (w, h) tuple (fit) or a dict with any of scale, max_dim, fit,
-        stretch, crop, cover, orient, qscale, sharpen, format (rendition_spec).  The entry of a raw rendition (format "rgb" /
+        stretch, crop, cover, orient, qscale, sharpen, format, pad (rendition_spec).  The entry of a raw rendition (format "rgb" /
         "rgb_planar") is a numpy uint8 array, (H, W, 3) / (3, H, W).  last_status has the result's shape.  out_cap: the
         output buffer size tried first (0: an estimate); renditions that did not fit (-50) make the call retry with a
         larger one -- raw renditions are then sized exactly, from the sizes the first pass reported."""
@@ -750,11 +838,11 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         cap = int(out_cap) or _multi_cap(streams, per_item, 1 << 20)
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
-        wh = (ctypes.c_int32 * (2 * total))() if opts._type_ is OutOpts6 else None  # the multi6 call reports the sizes
+        wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7) else None  # the multi6 / multi7 calls report the sizes
         jpeg_cap = cap
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            call = {OutOpts6: "h2j_engine_transcode_multi6", OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
+            call = {OutOpts7: "h2j_engine_transcode_multi7", OutOpts6: "h2j_engine_transcode_multi6", OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
             call = getattr(self._lib, call)
             rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
             small = [i for i in range(total) if status[i] == -50]
@@ -813,9 +901,9 @@ class Engine:
             cap = _multi_cap(streams, per_item, 2 << 20)
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
-            wh = (ctypes.c_int32 * (2 * total))() if opts._type_ is OutOpts6 else None
+            wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7) else None
             held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item, wh))
-            call = {OutOpts6: "h2j_engine_submit_multi6", OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
+            call = {OutOpts7: "h2j_engine_submit_multi7", OutOpts6: "h2j_engine_submit_multi6", OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
             call = getattr(self._lib, call)
             t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
             if t <= 0:
@@ -854,8 +942,10 @@ class Engine:
         `pick` of this picture with all of `renditions` (a list of specs) in flight; mode 0 unscaled,
         1..3 K3s at that scale, 4 K3r, 5 a level K3p wrote (include/h2j.h h2j_engine_decode_multi).
         Renditions with a crop or cover key go through decode_multi3, with an orient key through decode_multi4,
-        with a qscale or sharpen key through decode_multi5."""
+        with a qscale or sharpen key through decode_multi5, with a pad key through decode_multi7."""
         specs = normalize_renditions([list(renditions)], 1)[0]
+        if any(len(t) > 13 for t in specs):
+            return self.decode_multi7(stream, renditions, pick)[:5]
         if any(len(t) > 10 for t in specs):
             return self.decode_multi5(stream, renditions, pick)[:5]
         if any(len(t) > 9 for t in specs):
@@ -931,6 +1021,27 @@ class Engine:
         return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
                 int(info[8]), int(info[9]), int(info[10]), int(info[11]))
 
+    def decode_multi7(self, stream: bytes, renditions, pick: int):
+        """decode_multi through h2j_engine_decode_multi7 (padded output): decode_multi5's result -- the size is the
+        output's (the canvas of a padded rendition), the mode that of its picture part -- then whether the rendition was
+        padded (0: pad off, or nothing to pad), the place (px, py, w, h) of the picture part and the fill bytes
+        (Y, Cb, Cr).  The planes are what K4 reads: those of a padded rendition are the padded planes K3b wrote."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        total = len(specs)
+        opts = (OutOpts7 * total)(*[OutOpts7(*(tuple(t) + (0,) * 10)[:15]) for t in specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 18)()
+        rc = self._lib.h2j_engine_decode_multi7(self._h, buf, len(stream), total, opts, int(pick),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi7 failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
+                int(info[8]), int(info[9]), int(info[10]), int(info[11]), int(info[12]),
+                tuple(int(info[i]) for i in range(13, 17)), (info[17] & 255, (info[17] >> 8) & 255, (info[17] >> 16) & 255))
+
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
         return self._lib.h2j_engine_transcode(self._h, n, ptrs, sizes, out, cap, offs, lens, status)
@@ -953,7 +1064,7 @@ class Engine:
         return self._lib.h2j_engine_wait(self._h, int(ticket))
 
     def transcode_async(self, batches: Sequence[Sequence[bytes]], scale=None, max_dim=None, fit=None,
-                        stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None) -> List[List[Optional[bytes]]]:
+                        stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None, pad=None) -> List[List[Optional[bytes]]]:
         """Several batches through the asynchronous path, all submitted before the first wait.
 
         scale / max_dim as in transcode(): a scalar for every picture, or one entry per batch
@@ -961,13 +1072,15 @@ class Engine:
         every picture, or one entry per batch (each what transcode() takes).  crop / cover likewise: one
         window / box for every picture, or one entry per batch; orient likewise: one value (0..8 or "auto")
         for every picture, or one entry per batch; qscale and sharpen likewise: one int for every picture, or one
-        entry per batch; format likewise: one name for every picture, or one entry per batch."""
-        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format)):
+        entry per batch; format likewise: one name for every picture, or one entry per batch; pad likewise: True or one
+        (r, g, b) colour for every picture, or one entry per batch."""
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format, pad)):
+            one_pad = isinstance(pad, (bool, np.bool_)) or _is_colour(pad)
             one_orient = isinstance(orient, (str, int, np.integer))
             one_int = lambda v: isinstance(v, (int, np.integer))
             for name, v, one in (("crop", crop, _is_window(crop)), ("cover", cover, _is_pair(cover)), ("orient", orient, one_orient),
                                  ("qscale", qscale, one_int(qscale)), ("sharpen", sharpen, one_int(sharpen)),
-                                 ("format", format, isinstance(format, str))):
+                                 ("format", format, isinstance(format, str)), ("pad", pad, one_pad)):
                 if v is not None and not one and len(v) != len(batches):
                     raise ValueError(f"{name}: {len(v)} entries for {len(batches)} batches (one entry per batch)")
             pick = lambda v, one, bi: v if v is None or one else v[bi]
@@ -977,7 +1090,7 @@ class Engine:
                                    pick(fit, _is_pair(fit), bi), pick(stretch, isinstance(stretch, (bool, np.bool_)), bi),
                                    pick(crop, _is_window(crop), bi), pick(cover, _is_pair(cover), bi),
                                    pick(orient, one_orient, bi), pick(qscale, one_int(qscale), bi),
-                                   pick(sharpen, one_int(sharpen), bi), pick(format, isinstance(format, str), bi))
+                                   pick(sharpen, one_int(sharpen), bi), pick(format, isinstance(format, str), bi), pick(pad, one_pad, bi))
                      for bi, streams in enumerate(batches)]
             res = self._multi_async(batches, rends)
             self.last_status = [[st[0] for st in b] for b in self.last_status]
@@ -1104,9 +1217,10 @@ class Engine:
         return [(int(arr[3 * i]), arr[3 * i + 1], arr[3 * i + 2]) for i in range(min(n, cap))]
 
     def stats(self) -> dict:
-        arr = (ctypes.c_double * len(STAT_KEYS))()
-        self._lib.h2j_engine_stats(self._h, arr, len(STAT_KEYS))
-        return {k: arr[i] for i, k in enumerate(STAT_KEYS)}
+        keys = STAT_KEYS + STAT_KEYS_LATER
+        arr = (ctypes.c_double * len(keys))()
+        self._lib.h2j_engine_stats(self._h, arr, len(keys))
+        return {k: arr[i] for i, k in enumerate(keys)}
 
 
 def h265_to_jpeg(input_path: str, output_path: str) -> bool:

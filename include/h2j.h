@@ -331,6 +331,51 @@ int64_t h2j_engine_submit_multi6(h2j_engine *e, int n, const uint8_t *const *dat
                                  const int32_t *nrend, const h2j_out_opts6 *opts, uint8_t *out, size_t out_cap,
                                  size_t *out_off, size_t *out_len, int *status, int32_t *out_wh);
 
+/* Padded output: a rendition letterboxed to the exact size of its box (DESIGN.md "Padded output (K3b)").
+ * h2j_out_opts7 is h2j_out_opts6 with two of its reserved words named.
+ * pad: 0: off, as every other call.  1: the rendition is the box itself -- the picture part fitted inside it as the
+ *   same options without pad fit it, centred, the rest filled with `background`.  Needs a two-sided box: fit_w >= 2
+ *   and fit_h >= 2, with plain fit, H2J_FIT_STRETCH or H2J_FIT_COVER.
+ * background: 0x00RRGGBB, the fill colour (8-bit sRGB as JFIF carries it); 0 is black.
+ * The rule (all divisions floor): the picture part is the window, orientation and output ow x oh that
+ * h2j_crop_window6 gives for the options without pad (always even, always inside the box).  The canvas is
+ * BW = 2 (fit_w / 2), BH = 2 (fit_h / 2); the picture part sits at px = 2 ((BW - ow) / 4), py = 2 ((BH - oh) / 4)
+ * (both even: the chroma sits at px / 2, py / 2 of a BW/2 x BH/2 plane).  The fill colour is JFIF's forward matrix in
+ * 16.16, computed once on the host with arithmetic shifts (h2j_pad_colour):
+ *     Y  = (19595 R + 38470 G +  7471 B + 32768) >> 16
+ *     Cb = clip(((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128, 0, 255)
+ *     Cr = clip((( 32768 R - 27439 G -  5329 B + 32768) >> 16) + 128, 0, 255)
+ * so a grey (v, v, v) is (v, 128, 128), which the RGB formats turn back into (v, v, v) exactly.  The padded planes
+ * are 8-bit planes Y (BH x BW) full of Y and Cb, Cr (BH/2 x BW/2) full of Cb, Cr, with the rendition's final 8-bit
+ * planes -- after orientation, window, scale / fit and sharpen: the planes h2j_engine_decode_multi5 shows; the
+ * unsharp mask never sees the border -- written over the rectangle at (px, py).
+ * The padded planes are the picture: the rendition's bytes are exactly those the same call returns for a picture
+ * whose 8-bit planes are the padded planes -- rate control, qscale and format included; SOF0 and out_wh carry BW x BH.
+ * ow == BW and oh == BH: there is nothing to pad, and the rendition is the one without pad whatever background says.
+ * Not built: upscaling to fill the box, a gravity other than the centre.
+ * pad outside 0..1, background with bits above 23 set, background != 0 with pad 0, pad 1 without a two-sided box, a
+ * canvas above H2J_PAD_MAX_SAMPLES (below) or non-zero reserved: that rendition fails alone with H2J_ERR_OUT_OPTS.  On a kernel library without the stage
+ * (h2j_gpu_pad) a padded rendition fails alone with H2J_ERR_NO_STAGE.
+ * The functions that take h2j_out_opts7 are declared in include/h2j_ext.h and exported by libH265ToJpegExt.so: this
+ * header declares what libH265ToJpeg.so exports, and that list is fixed. */
+/* The largest canvas, in luma samples: BW x BH <= H2J_PAD_MAX_SAMPLES (8192 x 8192, or as many samples in another
+ * shape, e.g. 65534 x 1024).  Every other output is at most its decoded picture; a canvas is the caller's number, and it
+ * is device memory (about 14.5 bytes a sample for a JPEG rendition).  The bound also keeps the canvas planes' byte
+ * offsets -- at most 1.5 (BW + 15) BH < 2^27 -- far inside the int32 fields that carry them.  A padded rendition whose
+ * box is larger fails alone with H2J_ERR_OUT_OPTS, whatever the picture's size. */
+#define H2J_PAD_MAX_SAMPLES (1 << 26)
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts6 */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window of the oriented picture */
+    int32_t orient;                                   /* 0..8, or H2J_ORIENT_AUTO */
+    int32_t qscale;                                   /* 0, or 2..31 (0 with a raw format) */
+    int32_t sharpen;                                  /* 0..64, in 1/16 */
+    int32_t format;                                   /* H2J_FMT_* */
+    int32_t pad;                                      /* 0, or 1: letterbox to the box */
+    int32_t background;                               /* 0x00RRGGBB (0 without pad) */
+    int32_t reserved[1];                              /* must be 0 */
+} h2j_out_opts7;                                      /* 64 bytes */
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -383,7 +428,9 @@ int h2j_engine_decode_multi5(h2j_engine *e, const uint8_t *data, size_t size, in
  * picture of the batch: without the wait behind the previous batch)  [16..21] see STAT_KEYS in
  * h2j.py  [22] K3o / K3s / K3r / K3p / K3u orientation, scaled- and exact-size-output and finishing stage (GPU)  [23] renditions: JPEG outputs
  * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran
- * [25] raw bytes: the bytes of the raw (RGB) renditions delivered ([22] includes K3c, the RGB stage). */
+ * [25] raw bytes: the bytes of the raw (RGB) renditions delivered ([22] includes K3c, the RGB stage)
+ * [26] pad bytes: the canvas bytes K3b wrote for the padded renditions -- per canvas its three 8-bit planes, rows of
+ * whole 16-byte groups ([22] includes K3b, the padding stage). */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).

@@ -108,6 +108,11 @@ constexpr int h2j_k3u_tiles(int jpeg_w, int jpeg_h) {
 /* K3c (RGB output) workgroups (256 lanes: 64 lanes of 4 adjacent pixels x 4 lane rows; lane row j makes the output
  * rows 2 j - 1 and 2 j, which share the chroma rows j - 1 and j: h / 2 + 1 lane rows) of one w x h output */
 constexpr int h2j_k3c_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * (((h >> 1) + 1 + 3) >> 2); }
+/* K3b (padded output) workgroups (256 lanes: 64 dwords of 4 canvas samples x 4 lane rows of H2J_K3B_ROWS canvas rows
+ * each) of one canvas plane of w samples a row -- its rows' whole 16-byte groups are written -- and of a bw x bh canvas */
+#define H2J_K3B_ROWS 4
+constexpr int h2j_k3b_plane_tiles(int w, int h) { return (((h2j_spic_stride(w) >> 2) + 63) >> 6) * ((h + 4 * H2J_K3B_ROWS - 1) / (4 * H2J_K3B_ROWS)); }
+constexpr int h2j_k3b_tiles(int bw, int bh) { return h2j_k3b_plane_tiles(bw, bh) + 2 * h2j_k3b_plane_tiles(bw / 2, bh / 2); }
 /* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
  * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
@@ -246,6 +251,16 @@ int h2j_gpu_finish(const h2j_gpu_batch *b, const h2j_finish *map, const int32_t 
  * renditions alone (H2J_ERR_NO_STAGE) */
 #define H2J_RGB_CLASSES 3
 int h2j_gpu_rgb(const h2j_gpu_batch *b, const h2j_rgb *map, const int32_t *first, const int32_t *count,
+                const int32_t *tiles, void *stream);
+/* K3b: the padded outputs (h2j_pad, a device array), grouped by source class as K3u's (0: the 8-bit planes K3s / K3r /
+ * K3p / K3u wrote, h2j_pad.wide; 1: another 8-bit source; 2: a 16-bit source): the fill bytes and the source planes ->
+ * the canvas planes at h2j_pad.dst (DESIGN.md "Padded output (K3b)").  first / count / tiles: per class (host arrays
+ * of H2J_PAD_CLASSES), tiles the most workgroups one canvas of the class needs (h2j_k3b_tiles); one launch per class
+ * present.  Runs after h2j_gpu_finish, whose outputs it may read, and before h2j_gpu_rgb and K4, which may read the
+ * canvas; out of place.  A kernel library older than the stage lacks the symbol: the host library resolves it when it
+ * loads and fails padded renditions alone (H2J_ERR_NO_STAGE) */
+#define H2J_PAD_CLASSES 3
+int h2j_gpu_pad(const h2j_gpu_batch *b, const h2j_pad *map, const int32_t *first, const int32_t *count,
                 const int32_t *tiles, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat

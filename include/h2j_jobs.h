@@ -209,6 +209,29 @@ typedef struct {
     uint64_t dst_off;               /* byte offset of the pixels from that base (the arena: 256-byte aligned) */
 } h2j_rgb;
 
+/* One padded output of a batch (DESIGN.md "Padded output (K3b)"): K3b reads the planes the view of the output's
+ * picture part shows K4 -- the 8-bit planes K3s / K3r / K3p or K3u wrote (16-byte row groups), or an unscaled frame,
+ * window or oriented source in the frame's sample type -- and writes the canvas, 8-bit planes of its own at dst: every
+ * byte of their rows (row padding included) is the plane's fill byte, except the w x h rectangle at (px, py), which
+ * holds the picture part.  The record describes its source itself (no h2j_frame is read); K4 / K5 and K3c read dst
+ * through the canvas view (pic == pic2 == dst). */
+typedef struct {
+    int32_t w, h;                   /* luma size of the picture part (both even) */
+    int32_t bw, bh;                 /* luma size of the canvas (both even; w <= bw, h <= bh) */
+    int32_t px, py;                 /* the picture part's place in the canvas (both even; px + w <= bw, py + h <= bh) */
+    int32_t fill[3];                /* the fill bytes of the Y, Cb and Cr plane (0..255) */
+    int32_t bit_depth, bit_depth_c; /* of the source samples (8: uint8_t planes, above: uint16_t) */
+    int32_t crop_x, crop_y;         /* the source's first luma sample inside its planes */
+    int32_t wide;                   /* 1: an 8-bit source with 16-byte row groups and no crop (the planes K3s / K3r /
+                                       K3p / K3u wrote): aligned dword loads */
+    uint64_t src;                   /* source planes (arena offset, bytes) */
+    int32_t src_stride[3];          /* elements per row */
+    int32_t src_off[3];             /* element offset of each plane inside src */
+    uint64_t dst;                   /* canvas planes (arena offset, bytes; 256-byte aligned) */
+    int32_t dst_stride[3];          /* bytes per row (h2j_spic_stride: multiples of 16) */
+    int32_t dst_off[3];             /* byte offset of each plane inside dst */
+} h2j_pad;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;
