@@ -88,7 +88,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
                 // (a raw output reads any view with its planes: the quantiser scale does not change them; so does the
                 // canvas of a padded output.  A canvas view has the source -1: it is nobody's picture)
                 if (p.vsrc[v] == src && sv.scale_log2 == o.scale_log2 && (p.vqscale[v] == o.qscale || o.format || o.pad) && p.vsharpen[v] == o.sharpen &&
-                    (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
+                    p.vcolour[v] == o.colour && (o.scale_log2 != H2J_SCALE_RESAMPLE || (sv.jpeg_w == o.fit_w && sv.jpeg_h == o.fit_h)))
                     return static_cast<int>(v);
             }
             h2j_scaled sc{};
@@ -104,7 +104,31 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             p.qforced = p.qforced || (o.qscale != 0 && !o.pad);
             p.vjpeg.push_back(0);
             p.vpad.push_back(-1);
-            return static_cast<int>(p.scaled.size()) - 1;
+            p.vcolour.push_back(o.colour);
+            p.vcol.push_back(-1);
+            p.vshare.push_back(-1);
+            const int nv = static_cast<int>(p.scaled.size()) - 1;
+            if (!o.colour) return nv;
+            // a converted view: the record of an earlier view of the frame with its planes, or a new one; scaled planes
+            // an earlier view of the frame has are read, not made again
+            for (int u = static_cast<int>(v0); u < nv && p.vcol[nv] < 0; u++)
+                if (p.vcol[u] >= 0 && p.vsrc[u] == src && p.vcolour[u] == o.colour && p.scaled[u].scale_log2 == sc.scale_log2 &&
+                    p.scaled[u].jpeg_w == sc.jpeg_w && p.scaled[u].jpeg_h == sc.jpeg_h)
+                    p.vcol[nv] = p.vcol[u];
+            for (int u = static_cast<int>(v0); u < nv && sc.scale_log2 != 0 && p.vshare[nv] < 0; u++)
+                if (p.vsrc[u] == src && p.scaled[u].scale_log2 == sc.scale_log2 && p.scaled[u].jpeg_w == sc.jpeg_w && p.scaled[u].jpeg_h == sc.jpeg_h)
+                    p.vshare[nv] = p.vshare[u] >= 0 ? p.vshare[u] : u;
+            if (p.vcol[nv] < 0) {
+                h2j_colour rec{};
+                rec.w = sc.jpeg_w;
+                rec.h = sc.jpeg_h;
+                for (int i = 0; i < 8; i++) rec.k[i] = o.col_k[i];
+                rec.matrix = (rec.k[2] | rec.k[3] | rec.k[5] | rec.k[6]) ? 1 : 0;
+                p.vcol[nv] = static_cast<int>(p.cols.size());
+                p.cols.push_back(rec);
+                p.colview.push_back(nv);
+            }
+            return nv;
         };
         auto canvas_of = [&](const FrameJob::Output& o) {  // the canvas view of a padded output, added if new
             const int pv = view_of(o);
@@ -134,6 +158,9 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
             p.qforced = p.qforced || o.qscale != 0;
             p.vjpeg.push_back(0);
             p.vpad.push_back(static_cast<int>(p.pads.size()));
+            p.vcolour.push_back(0);
+            p.vcol.push_back(-1);
+            p.vshare.push_back(-1);
             p.pads.push_back(rec);
             p.padsrc.push_back(pv);
             p.padview.push_back(static_cast<int>(p.scaled.size()) - 1);
@@ -152,7 +179,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
         };
         for (int r = 0; r < j.nouts; r++)
             if (j.outs[r].error == 0 && j.outs[r].scale_log2 == 0 && !j.outs[r].windowed && !j.outs[r].orient && !j.outs[r].qscale &&
-                !j.outs[r].sharpen) {
+                !j.outs[r].sharpen && !j.outs[r].colour) {
                 view_of(j.outs[r]);
                 break;
             }
@@ -199,7 +226,7 @@ void number_frames_and_views(const std::vector<FrameJob>& jobs, const std::vecto
     p.at.bytes = c.off;  // the maps follow (layout_maps)
 }
 
-// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][bpic][rgb][jcoef][res][aux]
+// arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][vpic][upic][bpic][rgb][jcoef][res][aux]
 void layout_arena(ChunkPlan& p) {
     Cursor a;
     for (h2j_frame& f : p.frames) {
@@ -237,8 +264,18 @@ void layout_arena(ChunkPlan& p) {
             }
             (pass == 0 ? f.pic : f.pic2) = a.take((ysz + 2 * csz) * pel);
         }
-    for (h2j_scaled& sc : p.scaled) {  // the 8-bit scaled planes K3s / K3r / K3p write and K4 reads (scaled views only)
+    for (size_t v = 0; v < p.scaled.size(); v++) {  // the 8-bit scaled planes K3s / K3r / K3p write and K4 reads (scaled views only)
+        h2j_scaled& sc = p.scaled[v];
         if (sc.scale_log2 == 0) continue;
+        if (p.vshare[v] >= 0) {  // (a converted view that reads an earlier view's)
+            const h2j_scaled& su = p.scaled[p.vshare[v]];
+            sc.spic = su.spic;
+            for (int c = 0; c < 3; c++) {
+                sc.spic_stride[c] = su.spic_stride[c];
+                sc.spic_off[c] = su.spic_off[c];
+            }
+            continue;
+        }
         size_t po = 0;
         for (int c = 0; c < 3; c++) {
             const int pw = c ? sc.jpeg_w / 2 : sc.jpeg_w, ph = c ? sc.jpeg_h / 2 : sc.jpeg_h;
@@ -259,6 +296,19 @@ void layout_arena(ChunkPlan& p) {
             po += static_cast<size_t>(rec.stride[c]) * (c ? oh / 2 : oh);
         }
         rec.opic = a.take(po * pel);
+    }
+    p.colour_bytes = 0;
+    for (size_t i = 0; i < p.cols.size(); i++) {  // the 8-bit converted planes K3v writes (converted views only)
+        h2j_colour& rec = p.cols[i];
+        rec.jstat = p.scaled[p.colview[i]].jstat;
+        size_t po = 0;
+        for (int c = 0; c < 3; c++) {
+            rec.dst_stride[c] = h2j_spic_stride(c ? rec.w / 2 : rec.w);
+            rec.dst_off[c] = static_cast<int32_t>(po);
+            po += static_cast<size_t>(rec.dst_stride[c]) * (c ? rec.h / 2 : rec.h);
+        }
+        rec.dst = a.take(po);
+        p.colour_bytes += po;
     }
     for (int v = 0; v < p.nv; v++) {  // the 8-bit sharpened planes K3u writes and K4 reads (sharpened views only)
         p.vfin[v] = -1;
@@ -444,7 +494,7 @@ void build_scale_classes(ChunkPlan& p) {
         d.scale_first[cls] = static_cast<int>(p.scalemap.size());
         for (int v = 0; v < p.nv; v++) {
             const h2j_scaled& sc = p.scaled[v];
-            if (sc.scale_log2 == 0 || in_pyramid(v)) continue;  // unscaled, or K3p's
+            if (sc.scale_log2 == 0 || in_pyramid(v) || p.vshare[v] >= 0) continue;  // unscaled, K3p's, or another view's planes
             const int hbd = p.frames[sc.frame].bit_depth > 8 ? 1 : 0;
             const bool resample = sc.scale_log2 == H2J_SCALE_RESAMPLE;
             if ((resample ? H2J_K3R_CLASS0 + hbd : 3 * hbd + sc.scale_log2 - 1) != cls) continue;
@@ -487,20 +537,27 @@ void build_late_stage_maps(ChunkPlan& p) {
                           const bool tr = rec.orient >= 5;
                           return h2j_k3o_tiles(tr ? f.out_h : f.out_w, tr ? f.out_w : f.out_h, f.bit_depth > 8 ? 2 : 1, tr);
                       });
+    // K3v: the converted outputs with their sources (what each view is without colour and sharpening)
+    for (size_t i = 0; i < p.cols.size(); i++) {
+        const int v = p.colview[i];
+        fill_source(p.cols[i], p.scaled_view(v), p.scaled[v].scale_log2 != 0);
+    }
+    p.colmap.group(p.cols, [](const h2j_colour& rec) { return 2 * source_class(rec) + (rec.matrix ? 1 : 0); },
+                   [](const h2j_colour& rec) { return rec.matrix ? h2j_k3v_matrix_tiles(rec.w, rec.h) : h2j_k3v_range_tiles(rec.w, rec.h); });
     // K3u: the sharpened outputs with their sources (what each view is without its sharpening)
     for (int v = 0; v < p.nv; v++)
-        if (p.vfin[v] >= 0) fill_source(p.fins[p.vfin[v]], p.base_view(v), p.scaled[v].scale_log2 != 0);
+        if (p.vfin[v] >= 0) fill_source(p.fins[p.vfin[v]], p.base_view(v), p.scaled[v].scale_log2 != 0 || p.vcol[v] >= 0);
     p.finmap.group(p.fins, source_class<h2j_finish>, [](const h2j_finish& rec) { return h2j_k3u_tiles(rec.w, rec.h); });
     // K3b: the canvases with their sources (what view() shows K4 of the picture part)
     for (size_t i = 0; i < p.pads.size(); i++) {
         const int v = p.padsrc[i];
-        fill_source(p.pads[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0);
+        fill_source(p.pads[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0 || p.vcol[v] >= 0);
     }
     p.padmap.group(p.pads, source_class<h2j_pad>, [](const h2j_pad& rec) { return h2j_k3b_tiles(rec.bw, rec.bh); });
     // K3c: the raw outputs with their sources (what view() shows K4; a canvas is wide)
     for (size_t i = 0; i < p.rgbs.size(); i++) {
         const int v = p.rgbview[i];
-        fill_source(p.rgbs[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0 || p.vpad[v] >= 0);
+        fill_source(p.rgbs[i], p.view(v), p.scaled[v].scale_log2 != 0 || p.vfin[v] >= 0 || p.vpad[v] >= 0 || p.vcol[v] >= 0);
     }
     p.rgbmap.group(p.rgbs, source_class<h2j_rgb>, [](const h2j_rgb& rec) { return h2j_k3c_tiles(rec.w, rec.h); });
 }
@@ -531,6 +588,7 @@ void layout_maps(ChunkPlan& p) {
     p.at.jcompact = c.off;  // only in chunks with views that get no JPEG: the views K4 / K5 run on
     if (p.compact()) c.take(static_cast<size_t>(p.njpeg) * sizeof(h2j_frame));
     p.padmap.at = c.take(p.padmap.staging_bytes());  // behind everything else
+    p.colmap.at = c.take(p.colmap.staging_bytes());  // ... and the youngest behind that
     p.at.bytes = c.off;
 }
 
@@ -558,7 +616,7 @@ void fill_descriptor(ChunkPlan& p) {
     for (int v = 0; v < p.nv; v++)
         if (p.vjpeg[v])  // (K4 runs on the views that get a JPEG)
             d.k4a_frames += (h2j_sao_folds_variance(p.frames[p.scaled[v].frame]) && p.scaled[v].scale_log2 == 0 && p.vsrc[v] < p.nf && !p.vsharpen[v] &&
-                             p.vpad[v] < 0) ? 0 : 1;  // (a canvas: always K4a, on the padded planes)
+                             p.vpad[v] < 0 && p.vcol[v] < 0) ? 0 : 1;  // (a canvas, a converted view: always K4a, on those planes)
 }
 
 }  // namespace
@@ -593,7 +651,25 @@ h2j_frame ChunkPlan::view(int v) const {
     return shows(f, rec.dst, rec.w, rec.h, rec.dst_stride, rec.dst_off);
 }
 
+// A converted view is the 8-bit picture K3v writes at its h2j_colour record's dst, from what the view is without the
+// conversion (scaled_view)
 h2j_frame ChunkPlan::base_view(int v) const {
+    h2j_frame f = scaled_view(v);
+    if (vcol[v] < 0) return f;
+    const h2j_colour& rec = cols[vcol[v]];
+    f.pic = f.pic2 = rec.dst;  // pic == pic2: K4a sums the converted picture's MB variances
+    f.crop_x = f.crop_y = 0;
+    f.out_w = rec.w;
+    f.out_h = rec.h;
+    f.bit_depth = f.bit_depth_c = 8;
+    for (int c = 0; c < 3; c++) {
+        f.pic_stride[c] = rec.dst_stride[c];
+        f.pic_off[c] = rec.dst_off[c];
+    }
+    return f;
+}
+
+h2j_frame ChunkPlan::scaled_view(int v) const {
     const h2j_scaled& sc = scaled[v];
     h2j_frame f = frames[sc.frame];
     f.jcoef = vjcoef[v];
@@ -659,6 +735,7 @@ void ChunkPlan::reset(int nframes) {
     fstat.assign(static_cast<size_t>(nf), 0);
     clear_all(k1map, k1map8, k1all, k1hevc, saomap, scaled, scalemap, pyrmap, vsrc, wins, rends, jviews);
     clear_all(orients, orientmap, vqscale, vsharpen, fins, finmap, rgbs, rgbview, rgbmap, vjpeg, vpad, pads, padview, padsrc, padmap);
+    clear_all(vcolour, vcol, vshare, cols, colview, colmap);
     qforced = false;
     px = 0;
     std::memset(&desc, 0, sizeof(desc));
@@ -669,7 +746,8 @@ void plan_chunk(const std::vector<FrameJob>& jobs, const std::vector<int>& live,
     number_frames_and_views(jobs, live, p);
     // scaled pictures present, or several renditions of a frame: a views array is uploaded
     p.views = p.nv > p.nf || !p.wins.empty() || std::any_of(p.scaled.begin(), p.scaled.end(), [](const h2j_scaled& sc) { return sc.scale_log2 != 0; }) ||
-              std::any_of(p.vsharpen.begin(), p.vsharpen.end(), [](int a) { return a != 0; });  // ... or a sharpened view
+              std::any_of(p.vsharpen.begin(), p.vsharpen.end(), [](int a) { return a != 0; }) ||  // ... or a sharpened view
+              !p.cols.empty();  // ... or a converted one
     p.njpeg = static_cast<int>(std::count(p.vjpeg.begin(), p.vjpeg.end(), 1));
     for (int v = 0; v < p.nv && p.compact(); v++)
         if (p.vjpeg[v]) p.jviews.push_back(v);

@@ -20,7 +20,8 @@ constexpr size_t kSegBytesPerBlock = 272;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// The map of a late stage (K3o, K3u, K3b, K3c; include/h2j_gpu.h h2j_gpu_orient, h2j_gpu_finish, h2j_gpu_pad, h2j_gpu_rgb): the stage's
+// The map of a late stage (K3o, K3v, K3u, K3b, K3c; include/h2j_gpu.h h2j_gpu_orient, h2j_gpu_colour, h2j_gpu_finish, h2j_gpu_pad,
+// h2j_gpu_rgb): the stage's
 // records grouped by class, uploaded behind the other maps, with each class's first record, count and the most
 // workgroups one record of the class needs -- one launch per class present.  A chunk without the stage has an empty
 // map, uploads nothing for it and does not launch it
@@ -108,7 +109,7 @@ struct ChunkPlan {
     std::vector<h2j_finish> fins;    // the chunk's sharpened outputs, view-major
     StageMap<h2j_finish, H2J_FINISH_CLASSES> finmap;  // the same grouped by source class
     bool qforced = false;            // a view of the chunk forces its quantiser scale
-    h2j_frame base_view(int v) const;  // view v without its sharpening: what K3u reads
+    h2j_frame base_view(int v) const;  // view v without its sharpening: what K3u reads (a converted view: K3v's planes)
 
     // RGB output (K3c): a rendition has a format; a raw one (RGB pixels instead of a file) is served by a view like any
     // other -- the view of a JPEG rendition of the same frame with its (window, resolved output, sharpen) if there is
@@ -143,7 +144,24 @@ struct ChunkPlan {
     StageMap<h2j_pad, H2J_PAD_CLASSES> padmap;  // the same grouped by source class
     size_t pad_bytes = 0;          // the canvas bytes K3b writes (their planes' rows with the row padding)
 
-    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][upic][bpic][rgb][jcoef][res][aux]
+    // Colour (K3v): a view is (frame, window, resolved output, qscale, sharpen, resolved colour).  A converted view has a
+    // record: K3v reads what the view would be without the option and without sharpening (scaled_view: the scale
+    // stage's planes, or the frame, window or oriented source) and writes 8-bit planes of its own (vpic; the spic
+    // strides), which base_view() then shows with pic == pic2 -- so K3u, K3b, K3c and K4 see a wide source.  Converted
+    // views of one frame with one (source, resolved output, colour) -- they differ in qscale or sharpen -- share one
+    // record (vcol names it); a converted scaled view whose planes an earlier view of the frame has (the same source
+    // and output, converted or not) reads that view's (vshare) and is left out of the scale stage.  A chunk without
+    // converted outputs has none of this and uploads what it always did
+    std::vector<int> vcolour;       // per view: 0, or the resolved colour (FrameJob::Output::colour)
+    std::vector<int> vcol;          // per view: -1, or its record in cols
+    std::vector<int> vshare;        // per view: -1, or the earlier view whose scaled planes it reads
+    std::vector<h2j_colour> cols;   // the chunk's converted outputs, view-major
+    std::vector<int> colview;       // per converted output: the first view that shows it
+    StageMap<h2j_colour, H2J_COLOUR_CLASSES> colmap;  // the same grouped by class (2 x source class + work class)
+    size_t colour_bytes = 0;        // the plane bytes K3v writes (rows with the row padding)
+    h2j_frame scaled_view(int v) const;  // view v without colour and sharpening: what K3v reads
+
+    // arena layout: [zeroed: maps + CTB TU ranges + jstat][pic][pic2][spic][opic][vpic][upic][bpic][rgb][jcoef][res][aux]
     size_t arena_bytes = 0, zero_bytes = 0, jstat_base = 0, jstat_stride = 0;
     size_t seg_cap = 0;  // payload pool bytes (K5)
     int tiles = 0;       // 256-block tiles of the largest view (K5's tile_bits scratch: nv x tiles)

@@ -56,9 +56,9 @@ struct Request {
     const uint8_t* data = nullptr;
     size_t size = 0;
     // the options of the picture's renditions: one (all 0: the decoded size; h2j_h265_to_jpeg_mem_scaled,
-    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3 .. _multi7); per rendition the JPEG (a raw rendition: its
+    // _fit) or several (h2j_h265_to_jpeg_mem_multi, _multi3 .. _multi8); per rendition the JPEG (a raw rendition: its
     // pixels), the output's size and status once the batch ran
-    std::vector<h2j_out_opts7> opts{h2j_out_opts7{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}}};
+    std::vector<h2j_out_opts8> opts{h2j::kPlainOutput8};
     std::vector<std::vector<uint8_t>> jpegs;
     std::vector<int32_t> wh;
     std::vector<int> rstatus;
@@ -118,7 +118,7 @@ std::vector<std::vector<Request*>> split_lpt(const std::vector<Request*>& work, 
 }
 
 // run one batch (caller holds no lock); fills jpegs / rstatus / status / error of each request.  Every
-// picture is decoded once (h2j::submit_multi7, the transcode form; a plain request is an item with one rendition)
+// picture is decoded once (h2j::submit_multi8, the transcode form; a plain request is an item with one rendition)
 void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     const int n = static_cast<int>(batch.size());
     if (n == 0) return;
@@ -126,7 +126,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     std::vector<size_t> sizes(n);
     std::vector<int32_t> nrend(n);
     std::vector<int> base(n + 1, 0);
-    std::vector<h2j_out_opts7> opts;
+    std::vector<h2j_out_opts8> opts;
     size_t cap = 8u << 20;
     for (int i = 0; i < n; i++) {
         const Request* q = batch[i];
@@ -145,7 +145,7 @@ void run_batch(h2j_engine* e, std::vector<Request*>& batch) {
     int r = -1;
     for (int attempt = 0; attempt < 3; attempt++) {
         out.resize(cap);
-        r = static_cast<int>(h2j::submit_multi7(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
+        r = static_cast<int>(h2j::submit_multi8(e, n, ptrs.data(), sizes.data(), nrend.data(), opts.data(), out.data(), cap, off.data(),
                                                 len.data(), status.data(), wh.data(), true));
         bool small = false;
         size_t raw = 0;  // what the raw renditions need, exactly
@@ -298,7 +298,7 @@ static int to_jpeg_mem(const uint8_t* data, size_t size, const h2j_out_opts2& op
     Request req;
     req.data = data;
     req.size = size;
-    req.opts[0] = h2j::to_opts7(opts);
+    req.opts[0] = h2j::to_opts8(opts);
     if (!transcode_shared(req)) {
         LOG("transcode failed (%d): %s", req.status, req.error.c_str());
         return req.status ? req.status : -1;
@@ -322,8 +322,8 @@ extern "C" int h2j_h265_to_jpeg_mem_fit(const uint8_t* data, size_t size, int fi
     return to_jpeg_mem(data, size, h2j_out_opts2{0, 0, fit_w, fit_h, flags, {0, 0, 0}}, jpeg, jpeg_len);
 }
 
-// h2j_h265_to_jpeg_mem_multi7 (libH265ToJpegExt.so, api_ext.h), and what every older mem_multi call runs on
-int h2j::mem_multi7(const uint8_t* data, size_t size, int nrend, const h2j_out_opts7* opts, uint8_t** jpeg, size_t* jpeg_len, int* status,
+// h2j_h265_to_jpeg_mem_multi8 (libH265ToJpegExt.so, api_ext.h), and what every older mem_multi call runs on
+int h2j::mem_multi8(const uint8_t* data, size_t size, int nrend, const h2j_out_opts8* opts, uint8_t** jpeg, size_t* jpeg_len, int* status,
                     int32_t* out_wh) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!jpeg || !jpeg_len || !status || !opts) return -1;
@@ -365,7 +365,14 @@ static int to_jpeg_mem_multi(const uint8_t* data, size_t size, int nrend, const 
                              int32_t* out_wh = nullptr) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (!opts) return -1;
-    return h2j::mem_multi7(data, size, nrend, h2j::to_opts7(nrend, opts).data(), jpeg, jpeg_len, status, out_wh);
+    return h2j::mem_multi8(data, size, nrend, h2j::to_opts8(nrend, opts).data(), jpeg, jpeg_len, status, out_wh);
+}
+
+// h2j_h265_to_jpeg_mem_multi7 (libH265ToJpegExt.so, api_ext.h)
+int h2j::mem_multi7(const uint8_t* data, size_t size, int nrend, const h2j_out_opts7* opts, uint8_t** jpeg, size_t* jpeg_len, int* status,
+                    int32_t* out_wh) {
+    if (nrend >= 1 && nrend <= H2J_MAX_RENDITIONS && (!jpeg || !jpeg_len || !status)) return -1;
+    return to_jpeg_mem_multi(data, size, nrend, opts, jpeg, jpeg_len, status, out_wh);
 }
 
 extern "C" int h2j_h265_to_jpeg_mem_multi6(const uint8_t* data, size_t size, int nrend, const h2j_out_opts6* opts, uint8_t** jpeg,

@@ -28,7 +28,7 @@
 
 // The kernel library's optional late stages, null when the library in use is older than them (weak references:
 // bound when this library loads, so a stand-in or an older build selected beside it still loads): K3o; K3u and the
-// K4 entry that takes the quantiser scale from the caller; K3c; K3b
+// K4 entry that takes the quantiser scale from the caller; K3c; K3b; K3v
 extern "C" int h2j_gpu_orient(const h2j_gpu_batch*, const h2j_orient*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 extern "C" int h2j_gpu_finish(const h2j_gpu_batch*, const h2j_finish*, const int32_t*, const int32_t*, const int32_t*, void*)
@@ -37,6 +37,8 @@ extern "C" int h2j_gpu_jpeg2(const h2j_gpu_batch*, const int32_t*, void*) __attr
 extern "C" int h2j_gpu_rgb(const h2j_gpu_batch*, const h2j_rgb*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 extern "C" int h2j_gpu_pad(const h2j_gpu_batch*, const h2j_pad*, const int32_t*, const int32_t*, const int32_t*, void*)
+    __attribute__((weak));
+extern "C" int h2j_gpu_colour(const h2j_gpu_batch*, const h2j_colour*, const int32_t*, const int32_t*, const int32_t*, void*)
     __attribute__((weak));
 
 namespace h2j {
@@ -72,11 +74,14 @@ struct OptionalStage {
     const char* missing;
     int (*launch)(Engine&, Slot&);
 };
-enum { STAGE_ORIENT, STAGE_FINISH, STAGE_RGB, STAGE_PAD };
+enum { STAGE_ORIENT, STAGE_COLOUR, STAGE_FINISH, STAGE_RGB, STAGE_PAD };  // (checked and reported in this order: orient, colour, finish: the launch order)
 const OptionalStage kStages[] = {
     {[] { return h2j_gpu_orient != nullptr; }, [](const FrameJob::Output& o) { return o.orient != 0; },
      "the kernel library has no orientation stage (h2j_gpu_orient): oriented output needs a newer libh2j_hip.so",
      [](Engine& e, Slot& s) { return e.late_stage(s, s.plan.orientmap, h2j_gpu_orient, kStages[STAGE_ORIENT].missing); }},
+    {[] { return h2j_gpu_colour != nullptr; }, [](const FrameJob::Output& o) { return o.colour != 0; },
+     "the kernel library has no colour stage (h2j_gpu_colour): colour-converted output needs a newer libh2j_hip.so",
+     [](Engine& e, Slot& s) { return e.late_stage(s, s.plan.colmap, h2j_gpu_colour, kStages[STAGE_COLOUR].missing); }},
     {[] { return h2j_gpu_finish && h2j_gpu_jpeg2; }, [](const FrameJob::Output& o) { return o.qscale != 0 || o.sharpen != 0; },
      "the kernel library has no finishing stage (h2j_gpu_finish, h2j_gpu_jpeg2): qscale and sharpen need a newer libh2j_hip.so",
      [](Engine& e, Slot& s) { return e.late_stage(s, s.plan.finmap, h2j_gpu_finish, kStages[STAGE_FINISH].missing); }},
@@ -93,11 +98,11 @@ const char* no_stage_message(const FrameJob::Output& o) {
         if (st.needed(o) && !st.present()) return st.missing;
     return kStages[STAGE_RGB].missing;  // (asked of an output that lacks no stage: the last one's, as it always was)
 }
-void resolve_outputs(const h2j_out_opts7* o, int nr, FrameJob& job) {
+void resolve_outputs(const h2j_out_opts8* o, int nr, FrameJob& job) {
     job.nouts = nr;
     for (int r = 0; r < nr; r++) {
         job.outs[r] = FrameJob::Output();
-        if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h, job.sei_orient);
+        if (out_opts_valid(o[r])) job.outs[r] = resolve_output(o[r], job.hdr.out_w, job.hdr.out_h, job.sei_orient, job.colour);
         else job.outs[r].error = H2J_ERR_OUT_OPTS;
         for (const OptionalStage& st : kStages)
             if (job.outs[r].error == 0 && st.needed(job.outs[r]) && !st.present()) job.outs[r].error = H2J_ERR_NO_STAGE;
@@ -105,7 +110,7 @@ void resolve_outputs(const h2j_out_opts7* o, int nr, FrameJob& job) {
 }
 // parse one item of a batch with the output options of its nr renditions (a plain item: one).  The item
 // is not parsed when none is valid: it fails with the first one's message.  *ran: the entropy decode ran
-static int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts7* o, int nr, FrameJob& job, bool* ran) {
+static int parse_item_multi(const uint8_t* d, size_t n, const h2j_out_opts8* o, int nr, FrameJob& job, bool* ran) {
     *ran = std::any_of(o, o + nr, out_opts_valid);
     if (!*ran) {
         job.clear();
@@ -158,6 +163,7 @@ void Engine::pack_staging(Slot& s, bool pool_free) {
     put(p.finmap.at, p.finmap.map.data(), p.finmap.bytes());
     put(p.rgbmap.at, p.rgbmap.map.data(), p.rgbmap.bytes());
     put(p.padmap.at, p.padmap.map.data(), p.padmap.bytes());
+    put(p.colmap.at, p.colmap.map.data(), p.colmap.bytes());
     if (p.qforced && !p.compact()) put(p.at.qforce, p.vqscale.data(), static_cast<size_t>(p.nv) * 4);
     if (p.compact()) {  // the views K4 / K5 run on, and their forced scales, packed
         h2j_frame* jc = reinterpret_cast<h2j_frame*>(hin + p.at.jcompact);
@@ -257,6 +263,7 @@ int Engine::launch(Slot& s, const Slot* after) {
     // behind it
     if (kStages[STAGE_ORIENT].launch(*this, s)) return -1;
     if (s.stages >= 3 && h2j_gpu_scale(&b, st)) return drain_fail(s, h2j_gpu_last_error());  // K3s, K3r: no launch without scaled pictures
+    if (kStages[STAGE_COLOUR].launch(*this, s)) return -1;  // K3v: in front of K3u, which sharpens the converted planes
     if (kStages[STAGE_FINISH].launch(*this, s) || kStages[STAGE_PAD].launch(*this, s) || kStages[STAGE_RGB].launch(*this, s)) return -1;
     h2j_gpu_event_record(s.ev[EV_SCALE], st);
     // a chunk of raw renditions only: nobody asked for a JPEG, so no K4 / K5 and no payload (the pool's byte count,
@@ -337,6 +344,7 @@ int Engine::enqueue(Slot& s, int stages, bool entropy, bool pool_free, const Slo
     for (const h2j_frame& f : s.plan.frames) bytes += 1.5 * f.out_w * f.out_h * (4.0 + (f.bit_depth > 8 ? 2.0 : 1.0));
     stats[ST_BYTES] += bytes;
     if (s.stages >= 3) stats[ST_PAD_BYTES] += static_cast<double>(s.plan.pad_bytes);
+    if (s.stages >= 3) stats[ST_COLOUR_BYTES] += static_cast<double>(s.plan.colour_bytes);
     return 0;
 }
 
@@ -487,6 +495,9 @@ static double hbm_estimate(const FrameJob& j) {
     // pool, from the canvas size (one that shares a canvas with another rendition: an overestimate)
     for (int r = 0; r < j.nouts; r++)
         if (j.outs[r].error == 0 && j.outs[r].pad) est += 14.5 * j.outs[r].box_w * j.outs[r].box_h + 8192;
+    // converted outputs: the 8-bit planes K3v writes (one that shares them with another rendition: an overestimate)
+    for (int r = 0; r < j.nouts; r++)
+        if (j.outs[r].error == 0 && j.outs[r].colour) est += 1.5 * (j.outs[r].out_w() + 15.0) * j.outs[r].out_h() + 1024;
     return est;
 }
 // JPEG outputs of a job (at least one: the chunk bound counts a failed item as one; a padded output is two views)
@@ -580,7 +591,7 @@ void Engine::drive_loop() {
                 for (int o = b->rbase[i]; o < b->rbase[i + 1]; o++) {
                     if (b->status[o] == 0) continue;
                     if ((*jobs)[i].error != 0) b->msg[o] = (*jobs)[i].message;
-                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h, (*jobs)[i].sei_orient);
+                    else if (b->status[o] == H2J_ERR_OUT_OPTS) b->msg[o] = out_opts_message(b->opts[static_cast<size_t>(o)], (*jobs)[i].hdr.out_w, (*jobs)[i].hdr.out_h, (*jobs)[i].sei_orient, (*jobs)[i].colour);
                     else if (b->status[o] == H2J_ERR_NO_STAGE) b->msg[o] = no_stage_message((*jobs)[i].outs[o - b->rbase[i]]);
                 }
             }

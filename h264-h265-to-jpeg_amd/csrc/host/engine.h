@@ -48,7 +48,7 @@ enum {
     EV_K1,
     EV_K2,
     EV_K3,
-    EV_SCALE,       // after K3o (oriented output), K3s / K3r / K3p (scaled output), K3u (finishing), K3b (padded output) and K3c (RGB output)
+    EV_SCALE,       // after K3o (oriented output), K3s / K3r / K3p (scaled output), K3v (colour), K3u (finishing), K3b (padded output) and K3c (RGB output)
     EV_K4,
     EV_K5,          // the last kernel: the other slot's next chunk waits for it
     EV_STATS,       // after the stats D2H
@@ -103,9 +103,10 @@ struct Slot {
 // 
 enum { ST_PARSE, ST_H2D, ST_RECON, ST_DEBLOCK, ST_SAO, ST_JPEG, ST_D2H, ST_ASSEMBLE, ST_TOTAL, ST_FRAMES, ST_BYTES,
        ST_ENTROPY, ST_PREP, ST_CHUNKS, ST_PACK, ST_PARSE_RUN, ST_D2H_STATS, ST_D2H_PAY, ST_PAY_BYTES, ST_HOST_GROW,
-       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_RAW_BYTES, ST_PAD_BYTES, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3o + K3s + K3r + K3p + K3u + K3b + K3c
+       ST_H2D_BYTES, ST_PAY_COPIED, ST_SCALE, ST_RENDITIONS, ST_PARSED, ST_RAW_BYTES, ST_PAD_BYTES, ST_COLOUR_BYTES, ST_N };  // ST_PACK: host time packing records into staging; ST_SCALE: K3o + K3s + K3r + K3p + K3v + K3u + K3b + K3c
 // ST_RAW_BYTES: bytes of the raw (RGB) renditions delivered; K3c's time counts in ST_SCALE
 // ST_PAD_BYTES: canvas bytes K3b wrote for the padded renditions; K3b's time counts in ST_SCALE
+// ST_COLOUR_BYTES: plane bytes K3v wrote for the colour-converted renditions; K3v's time counts in ST_SCALE
 // ST_RENDITIONS: JPEG outputs of the batch (ST_FRAMES: decoded pictures); ST_PARSED: pictures whose entropy decode ran
 
 struct ChunkTime {
@@ -126,7 +127,7 @@ struct Batch {
     int* status = nullptr;
     int32_t* out_wh = nullptr;                 // per rendition: its output's W, H (may be null)
     size_t raw_planned = 0;                    // bytes of the raw renditions the chunks planned so far hold
-    std::vector<h2j_out_opts7> opts;           // output options per rendition, item-major (a plain item has one rendition)
+    std::vector<h2j_out_opts8> opts;           // output options per rendition, item-major (a plain item has one rendition)
     std::vector<int> rbase;                    // first rendition of each item, n + 1 entries
     int nout = 0;                              // entries of opts / out_off / out_len / status: rbase[n]
     std::atomic<int> nparsed{0};               // items whose entropy decode ran
@@ -249,7 +250,7 @@ struct Engine {
 int parse_any(const uint8_t* d, size_t n, FrameJob& job);
 // the outputs of a parsed job: every rendition's is resolved on its own (out_opts.h), and invalid options or a
 // stage the kernel library lacks (H2J_ERR_NO_STAGE) fail that rendition alone
-void resolve_outputs(const h2j_out_opts7* o, int nr, FrameJob& job);
+void resolve_outputs(const h2j_out_opts8* o, int nr, FrameJob& job);
 // the message of an output that failed with H2J_ERR_NO_STAGE: the stage the kernel library lacks
 const char* no_stage_message(const FrameJob::Output& o);
 std::vector<int> chunk_bounds(int n);             // the synchronous plan: a shrinking tail

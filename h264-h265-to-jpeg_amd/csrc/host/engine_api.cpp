@@ -20,7 +20,7 @@ struct h2j_engine {
 // Item i has nrend[i] renditions (null: one each); opts and the output arrays are item-major over all of
 // them (opts null: the decoded size)
 static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend,
-                            const h2j_out_opts7* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
+                            const h2j_out_opts8* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                             int* status, bool latency, int32_t* out_wh = nullptr) {
     Engine& e = w->e;
     std::unique_ptr<h2j::Batch> b(new h2j::Batch());
@@ -37,7 +37,7 @@ static int64_t submit_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     for (int i = 0; i < n; i++) b->rbase[i + 1] = b->rbase[i] + (nrend ? nrend[i] : 1);
     b->nout = b->rbase[n];
     if (opts) b->opts.assign(opts, opts + b->nout);
-    else b->opts.assign(static_cast<size_t>(b->nout), h2j::kPlainOutput7);
+    else b->opts.assign(static_cast<size_t>(b->nout), h2j::kPlainOutput8);
     for (int i = 0; i < b->nout; i++) {
         out_len[i] = 0;
         out_off[i] = 0;
@@ -81,12 +81,12 @@ static int64_t submit_multi_any(h2j_engine* w, int n, const uint8_t* const* data
     if (!renditions_valid(n, nrend, opts)) return H2J_ERR_RENDITIONS;
     int total = 0;
     for (int i = 0; i < n; i++) total += nrend[i];
-    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::to_opts7(total, opts).data(), out, out_cap, out_off, out_len, status, latency, out_wh);
+    const int64_t t = submit_batch(w, n, data, sizes, nrend, h2j::to_opts8(total, opts).data(), out, out_cap, out_off, out_len, status, latency, out_wh);
     return latency ? h2j_engine_wait(w, t) : t;
 }
 
 // parse one picture into jobs[0] of slot 0, with the outputs of its nrend option sets (valid ones)
-static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts7* o = &h2j::kPlainOutput7, int nrend = 1) {
+static int single_job(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts8* o = &h2j::kPlainOutput8, int nrend = 1) {
     Engine& e = w->e;
     e.quiesce();
     if (h2j_gpu_set_device(e.device)) return e.fail(h2j_gpu_last_error());
@@ -134,8 +134,8 @@ static int copy_planes(Engine& e, Slot& s, int k, int stage, uint16_t* planes_ou
 // the 8-bit planes K4 reads for one picture with output options o (h2j_engine_decode_scaled / _resized)
 // (nrend renditions in flight, planes of rendition `pick`: h2j_engine_decode_multi)
 // (info_n: entries of info the call has -- 4; 8: the window; 10: the orientation too; 12: qscale and sharpen too; 18: the
-// padding too)
-static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts7* o, int nrend, int pick,
+// padding too; 21: the colour too)
+static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, const h2j_out_opts8* o, int nrend, int pick,
                               uint8_t* planes_out, size_t cap, int* info, int info_n = 4) {
     if (!w || !data || !planes_out || !info || !o) return -1;
     Engine& e = w->e;
@@ -150,7 +150,7 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
             e.fail(h2j::no_stage_message(e.jobs[0].outs[r]));
             return H2J_ERR_NO_STAGE;
         } else if (e.jobs[0].outs[r].error) {  // a window outside the picture
-            e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h, e.jobs[0].sei_orient));
+            e.fail(h2j::out_opts_message(o[r], e.jobs[0].hdr.out_w, e.jobs[0].hdr.out_h, e.jobs[0].sei_orient, e.jobs[0].colour));
             return H2J_ERR_OUT_OPTS;
         }
     Slot& s = e.slot[0];
@@ -198,12 +198,17 @@ static int decode_jpeg_source(h2j_engine* w, const uint8_t* data, size_t size, c
         info[16] = wo.out_h();
         info[17] = wo.fill[0] | (wo.fill[1] << 8) | (wo.fill[2] << 16);
     }
+    if (info_n >= 21) {
+        info[18] = wo.col_matrix;
+        info[19] = wo.col_full;
+        info[20] = wo.colour ? 1 : 0;
+    }
     if (cap < static_cast<size_t>(w_) * h_ * 3 / 2) return e.fail("output buffer too small");
     const size_t pel = v.bit_depth > 8 ? 2 : 1;
     size_t bytes = 0;  // the view's planes in the arena, from v.pic2
     for (int c = 0; c < 3; c++) {
         // (an unscaled oriented view lies in the oriented planes, whose rows end with the oriented picture's)
-        const int rows = (sc.scale_log2 || wo.sharpen || padded) ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
+        const int rows = (sc.scale_log2 || wo.sharpen || padded || wo.colour) ? (h_ >> (c ? 1 : 0)) : wo.orient ? ((v.crop_y + h_) >> (c ? 1 : 0)) : (f.height >> (c ? 1 : 0));
         bytes = std::max(bytes, (static_cast<size_t>(v.pic_off[c]) + static_cast<size_t>(v.pic_stride[c]) * rows) * pel);
     }
     std::vector<uint8_t> tmp(bytes);
@@ -231,10 +236,10 @@ static int decode_multi_any(h2j_engine* w, const uint8_t* data, size_t size, int
                             size_t cap, int* info, int info_n) {
     if (nrend < 1 || nrend > H2J_MAX_RENDITIONS) return H2J_ERR_RENDITIONS;
     if (pick < 0 || pick >= nrend || !opts) return -1;
-    return decode_jpeg_source(w, data, size, h2j::to_opts7(nrend, opts).data(), nrend, pick, planes_out, cap, info, info_n);
+    return decode_jpeg_source(w, data, size, h2j::to_opts8(nrend, opts).data(), nrend, pick, planes_out, cap, info, info_n);
 }
 
-// the engine calls of libH265ToJpegExt.so (api_ext.h): the multi6 calls with h2j_out_opts7
+// the engine calls of libH265ToJpegExt.so (api_ext.h): the multi6 calls with h2j_out_opts7 and h2j_out_opts8
 namespace h2j {
 int64_t submit_multi7(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend, const h2j_out_opts7* opts,
                       uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len, int* status, int32_t* out_wh, bool latency) {
@@ -243,6 +248,31 @@ int64_t submit_multi7(h2j_engine* w, int n, const uint8_t* const* data, const si
 int decode_multi7(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts7* opts, int pick, uint8_t* planes_out,
                   size_t cap, int* info) {
     return decode_multi_any(w, data, size, nrend, opts, pick, planes_out, cap, info, 18);
+}
+int64_t submit_multi8(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes, const int32_t* nrend, const h2j_out_opts8* opts,
+                      uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len, int* status, int32_t* out_wh, bool latency) {
+    return submit_multi_any(w, n, data, sizes, nrend, opts, out, out_cap, out_off, out_len, status, latency, out_wh);
+}
+int decode_multi8(h2j_engine* w, const uint8_t* data, size_t size, int nrend, const h2j_out_opts8* opts, int pick, uint8_t* planes_out,
+                  size_t cap, int* info) {
+    return decode_multi_any(w, data, size, nrend, opts, pick, planes_out, cap, info, 21);
+}
+int stream_colour(const uint8_t* data, size_t size, int32_t* info) {
+    if (!data || !info) return -1;
+    int c[4] = {2, 2, 2, 0};
+    int rc = 0;
+    if (is_heif(data, size)) {
+        rc = heif_stream_colour(data, size, c);
+    } else {
+        const int codec = detect_codec(data, size);
+        if (codec != 264 && codec != 265) return -100;
+        // (a stream without an SPS that parses signals nothing)
+        if (codec == 265) hevc_stream_colour(data, size, c);
+        else h264_stream_colour(data, size, c);
+    }
+    if (rc) return rc;
+    for (int i = 0; i < 4; i++) info[i] = c[i];
+    return 0;
 }
 }  // namespace h2j
 
@@ -303,14 +333,14 @@ int64_t h2j_engine_submit_opts(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                                int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts8(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int64_t h2j_engine_submit_opts2(h2j_engine* w, int n, const uint8_t* const* data, const size_t* sizes,
                                 const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                 size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, false);
+    return submit_batch(w, n, data, sizes, nullptr, h2j::to_opts8(n, opts).data(), out, out_cap, out_off, out_len, status, false);
 }
 
 int h2j_engine_wait(h2j_engine* w, int64_t ticket) {
@@ -343,7 +373,7 @@ int h2j_engine_transcode_opts(h2j_engine* w, int n, const uint8_t* const* data, 
                               const h2j_out_opts* opts, uint8_t* out, size_t out_cap, size_t* out_off, size_t* out_len,
                               int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts8(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -351,7 +381,7 @@ int h2j_engine_transcode_opts2(h2j_engine* w, int n, const uint8_t* const* data,
                                const h2j_out_opts2* opts, uint8_t* out, size_t out_cap, size_t* out_off,
                                size_t* out_len, int* status) {
     if (!w || n < 0) return -1;
-    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts7(n, opts).data(), out, out_cap, out_off, out_len, status, true);
+    const int64_t t = submit_batch(w, n, data, sizes, nullptr, h2j::to_opts8(n, opts).data(), out, out_cap, out_off, out_len, status, true);
     return h2j_engine_wait(w, t);
 }
 
@@ -441,7 +471,7 @@ int h2j_engine_decode_batch(h2j_engine* w, int n, const uint8_t* const* data, co
     e.par(n, [&](int i) {
         e.jobs[i].threads = 1;
         rc[i] = h2j::parse_any(data[i], sizes[i], e.jobs[i]);
-        if (rc[i] == 0) h2j::resolve_outputs(&h2j::kPlainOutput7, 1, e.jobs[i]);
+        if (rc[i] == 0) h2j::resolve_outputs(&h2j::kPlainOutput8, 1, e.jobs[i]);
     });
     for (int i = 0; i < n; i++)
         if (rc[i]) {
@@ -481,13 +511,13 @@ int h2j_engine_jpeg_coeffs(h2j_engine* w, const uint8_t* data, size_t size, int1
 
 int h2j_engine_decode_scaled(h2j_engine* w, const uint8_t* data, size_t size, int scale_log2, int max_dim,
                              uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts7 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
+    const h2j_out_opts8 o = {scale_log2, max_dim, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 
 int h2j_engine_decode_resized(h2j_engine* w, const uint8_t* data, size_t size, int fit_w, int fit_h, int flags,
                               uint8_t* planes_out, size_t cap, int* info) {
-    const h2j_out_opts7 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
+    const h2j_out_opts8 o = {0, 0, fit_w, fit_h, flags, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     return decode_jpeg_source(w, data, size, &o, 1, 0, planes_out, cap, info);
 }
 

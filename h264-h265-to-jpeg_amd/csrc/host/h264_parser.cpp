@@ -124,6 +124,9 @@ struct Sps {
     int transform_bypass = 0;        // qpprime_y_zero_transform_bypass_flag
     int crop_l = 0, crop_r = 0, crop_t = 0, crop_b = 0;
     int num_reorder_frames = 0;  // VUI bitstream_restriction (0 when absent)
+    // VUI video_signal_type: colour_primaries, transfer_characteristics, matrix_coefficients, video_full_range_flag
+    // (2, 2, 2, 0 where absent: FrameJob::colour)
+    int colour[4] = {2, 2, 2, 0};
     bool scaling_present = false;
     uint8_t sl4[6][16];
     uint8_t sl8[6][64];
@@ -149,12 +152,14 @@ bool skip_hrd(BitReader& b) {
 // the VUI carries none or is truncated (FFmpeg then keeps no delay either), -1 where FFmpeg 4.3
 // h264_ps.c fails the SPS: an HRD with more than 32 CPBs, or max_num_reorder_frames > 16
 // ("Clipping illegal num_reorder_frames", AVERROR_INVALIDDATA).
-int parse_vui_reorder(BitReader& b) {
+// colour: what video_signal_type says (Sps::colour), kept for the colour option; the walk reads the bits it always read
+int parse_vui_reorder(BitReader& b, int* colour) {
     if (b.u(1) && b.u(8) == 255) b.u(32);  // aspect_ratio_idc, Extended_SAR
     if (b.u(1)) b.u(1);                    // overscan
     if (b.u(1)) {                          // video_signal_type
-        b.u(4);
-        if (b.u(1)) b.u(24);
+        colour[3] = static_cast<int>(b.u(4) & 1);  // video_format (3), video_full_range_flag
+        if (b.u(1))
+            for (int i = 0; i < 3; i++) colour[i] = static_cast<int>(b.u(8));
     }
     if (b.u(1)) {  // chroma_loc_info
         b.ue();
@@ -298,7 +303,7 @@ int parse_sps(BitReader& b, Sps* tab) {
     }
     if (b.overrun()) return -1;
     if (b.u(1)) {
-        s.num_reorder_frames = parse_vui_reorder(b);
+        s.num_reorder_frames = parse_vui_reorder(b, s.colour);
         if (s.num_reorder_frames < 0) return -1;
     }
     // FFmpeg 4.3 decodes 4:2:0 and 4:0:0 (into yuv420p) at 8, 9, 10, 12 and 14 bits with equal
@@ -1470,6 +1475,7 @@ int H264Parser::run(const uint8_t* data, size_t size, int threads) {
             if (!have) {
                 s_ = &s;
                 job_->reorder_delay = s.num_reorder_frames > 0;
+                std::copy(s.colour, s.colour + 4, job_->colour);
                 mbw_ = s.mb_w;
                 mbh_ = s.mb_h;
                 mbaff_ = s.mbaff || field_pic;  // MbaffFrameFlag; a field pair uses the same layout
@@ -1663,6 +1669,27 @@ int H264Parser::decode_slice(const SliceWork& w) {
 }
 
 }  // namespace
+
+// what the first SPS of an Annex-B stream that parses signals of its colour (FrameJob::colour); false: none does
+bool h264_stream_colour(const uint8_t* data, size_t size, int* colour) {
+    std::vector<Nal> nals;
+    split_annexb(data, size, nals);
+    std::vector<uint8_t> rbsp;
+    std::unique_ptr<Sps[]> tab(new Sps[32]);
+    for (const Nal& nal : nals) {
+        if (nal.n < 2 || (nal.p[0] & 31) != 7) continue;
+        rbsp.resize(nal.n + 16);
+        const size_t rn = unescape_rbsp(nal.p + 1, nal.n - 1, rbsp.data());
+        BitReader b(rbsp.data(), rn);
+        if (parse_sps(b, tab.get()) < 0) continue;
+        for (int i = 0; i < 32; i++)
+            if (tab[i].valid) {
+                std::copy(tab[i].colour, tab[i].colour + 4, colour);
+                return true;
+            }
+    }
+    return false;
+}
 
 int h264_parse_picture(const uint8_t* data, size_t size, FrameJob& job) {
     job.clear();

@@ -382,6 +382,21 @@ int Demux::check_properties(const Item& it, const Prop** config, bool orient) {
             return r_.error;
         }
         if ((p.type == cc4('h', 'v', 'c', 'C') || p.type == cc4('a', 'v', 'c', 'C')) && !*config) *config = &p;
+        if (p.type == cc4('c', 'o', 'l', 'r') && !r_.nclx) {
+            // the first nclx met: the primary item's properties are walked first, a grid's tiles' after the grid's own.
+            // A colr that is short or of another type changes nothing, as it never did
+            Rd c(d_, p.body, p.end);
+            const uint32_t kind = static_cast<uint32_t>(c.be(4));
+            const int pri = static_cast<int>(c.be(2)), trc = static_cast<int>(c.be(2)), mat = static_cast<int>(c.be(2));
+            const int full = static_cast<int>(c.be(1) >> 7);
+            if (!c.bad && kind == cc4('n', 'c', 'l', 'x')) {
+                r_.nclx = true;
+                r_.colour[0] = pri;
+                r_.colour[1] = trc;
+                r_.colour[2] = mat;
+                r_.colour[3] = full;
+            }
+        }
         if (!orient) continue;
         Rd q(d_, p.body, p.end);
         if (p.type == cc4('i', 'r', 'o', 't')) {

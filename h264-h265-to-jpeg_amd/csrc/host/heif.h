@@ -25,6 +25,10 @@ struct HeifResult {
     bool grid = false;  // a grid of rows x cols tiles whose output is out_w x out_h
     int rows = 1, cols = 1, out_w = 0, out_h = 0;
     int orient = 0;     // irot / imir of the primary item as an orientation 0, 2..8 (include/h2j.h)
+    // the `nclx` colr property of the primary item (a grid without one: the first its tiles carry): colour_primaries,
+    // transfer_characteristics, matrix_coefficients, full_range_flag.  rICC / prof profiles are ignored
+    bool nclx = false;
+    int colour[4] = {2, 2, 2, 0};
     // the Annex-B streams, one per tile in raster order (a single item: one), back to back:
     // stream t is bytes[tile_off[t] .. tile_off[t + 1])
     std::vector<uint8_t> bytes;

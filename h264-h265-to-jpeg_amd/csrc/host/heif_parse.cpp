@@ -1,4 +1,6 @@
 // HEIF input to job records: the demuxer (heif.cpp) in front of the entropy decoders.
+#include <algorithm>
+
 #include "bitstream.h"
 #include "heif.h"
 #include "job.h"
@@ -31,7 +33,22 @@ int heif_parse_picture(const uint8_t* data, size_t size, FrameJob& job) {
     // the file's transform properties say how to show the picture; a display orientation SEI inside the item
     // stands only where the file has none (a grid's tiles' SEI messages are never read)
     if (rc == 0 && r.orient) job.sei_orient = r.orient;
+    // likewise the file's nclx colour property wins over the VUI of the item's SPS
+    if (rc == 0 && r.nclx) std::copy(r.colour, r.colour + 4, job.colour);
     return rc;
+}
+
+int heif_stream_colour(const uint8_t* data, size_t size, int* colour) {
+    HeifResult r;
+    if (heif_demux(data, size, r)) return r.error;
+    if (r.nclx) {
+        std::copy(r.colour, r.colour + 4, colour);
+        return 0;
+    }
+    // (a grid: tile 0's stream -- the tiles' parameter sets are equal)
+    const size_t n0 = r.tile_off.size() > 1 ? static_cast<size_t>(r.tile_off[1] - r.tile_off[0]) : r.bytes.size();
+    const bool ok = r.codec == 265 ? hevc_stream_colour(r.bytes.data(), n0, colour) : h264_stream_colour(r.bytes.data(), n0, colour);
+    return ok ? 0 : -100;
 }
 
 int heif_orientation(const uint8_t* data, size_t size) {

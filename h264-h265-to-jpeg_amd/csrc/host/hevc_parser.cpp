@@ -66,6 +66,9 @@ struct Sps {
     // sps_range_extension (H.265 v2 7.3.2.2.2)
     int ts_rotation = 0, ts_context = 0, implicit_rdpcm = 0, explicit_rdpcm = 0, ext_precision = 0;
     int smoothing_disabled = 0, high_prec_offsets = 0, persistent_rice = 0, bypass_alignment = 0;
+    // VUI video_signal_type: colour_primaries, transfer_characteristics, matrix_coefficients, video_full_range_flag
+    // (2, 2, 2, 0 where absent: FrameJob::colour)
+    int colour[4] = {2, 2, 2, 0};
 };
 
 struct Pps {
@@ -199,13 +202,15 @@ bool skip_hrd(BitReader& b, int max_sub_layers) {
 }
 
 // vui_parameters (E.2.1), skipped: nothing in it changes decoded samples (FFmpeg applies the default
-// display window only with its apply_defdispwin option, off by default)
-bool skip_vui(BitReader& b, int max_sub_layers) {
+// display window only with its apply_defdispwin option, off by default).  colour: what video_signal_type says
+// (Sps::colour), kept for the colour option; the walk reads the bits it always read
+bool skip_vui(BitReader& b, int max_sub_layers, int* colour) {
     if (b.u(1) && b.u(8) == 255) b.u(32);
     if (b.u(1)) b.u(1);
     if (b.u(1)) {
-        b.u(4);
-        if (b.u(1)) b.u(24);
+        colour[3] = static_cast<int>(b.u(4) & 1);  // video_format (3), video_full_range_flag
+        if (b.u(1))
+            for (int i = 0; i < 3; i++) colour[i] = static_cast<int>(b.u(8));
     }
     if (b.u(1)) { b.ue(); b.ue(); }
     b.u(3);
@@ -329,7 +334,7 @@ int parse_sps(BitReader& b, Sps* tab) {
     }
     s.temporal_mvp = static_cast<int>(b.u(1));
     s.strong_intra_smoothing = static_cast<int>(b.u(1));
-    if (b.u(1) && !skip_vui(b, msl + 1)) return -1;
+    if (b.u(1) && !skip_vui(b, msl + 1, s.colour)) return -1;
     if (b.u(1)) {                                    // sps_extension_present_flag
         const int range = static_cast<int>(b.u(1));  // sps_range_extension_flag
         b.u(7);                                      // multilayer / 3d / scc / 4bits: not read (FFmpeg 4.3)
@@ -1997,6 +2002,7 @@ int HevcParser::run(const uint8_t* data, size_t size, int threads) {
                 s_ = &sps_[p_->sps_id];
                 if (!setup_picture()) { job_->message = "invalid tile grid"; return -6; }
                 job_->reorder_delay = s_->num_reorder_pics > 0;
+                std::copy(s_->colour, s_->colour + 4, job_->colour);
                 have_pic = true;
             }
             // all slice segments of a picture use one PPS (7.4.7.1; FFmpeg: "PPS changed between
@@ -2237,6 +2243,7 @@ int HevcParser::run_grid(const uint8_t* const* tiles, const size_t* sizes, int r
     s_ = &cs;
     if (!setup_picture()) return fail(-6, "invalid tile grid");
     job_->reorder_delay = s_->num_reorder_pics > 0;
+    std::copy(s_->colour, s_->colour + 4, job_->colour);
     // canvas slices: slice_segment_address in the tile picture's raster scan is the offset in the tile's tile scan
     const int ns = static_cast<int>(sh_.size());
     std::vector<int> ts0(ns), ts1(ns);
@@ -2312,6 +2319,27 @@ int hevc_parse_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, 
     const int r = p->run_grid(tiles, sizes, rows, cols, out_w, out_h, job.threads);
     job.error = r;
     return r;
+}
+
+// what the first SPS of an Annex-B stream that parses signals of its colour (FrameJob::colour); false: none does
+bool hevc_stream_colour(const uint8_t* data, size_t size, int* colour) {
+    std::vector<Nal> nals;
+    split_annexb(data, size, nals);
+    std::vector<uint8_t> rbsp;
+    std::unique_ptr<Sps[]> tab(new Sps[16]);
+    for (const Nal& nal : nals) {
+        if (nal.n < 2 || ((nal.p[0] >> 1) & 63) != 33) continue;
+        rbsp.resize(nal.n + 16);
+        const size_t rn = unescape_rbsp(nal.p + 2, nal.n - 2, rbsp.data());
+        BitReader b(rbsp.data(), rn);
+        if (parse_sps(b, tab.get()) < 0) continue;
+        for (int i = 0; i < 16; i++)
+            if (tab[i].valid) {
+                std::copy(tab[i].colour, tab[i].colour + 4, colour);
+                return true;
+            }
+    }
+    return false;
 }
 
 int hevc_parse_picture(const uint8_t* data, size_t size, FrameJob& job) {

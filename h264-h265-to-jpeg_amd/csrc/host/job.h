@@ -31,6 +31,10 @@ struct FrameJob {
     // the display orientation SEI in front of the picture's first slice as an orientation 0, 2..8
     // (include/h2j.h "Orientation"; 0: none, cancelled or unusable).  Only H2J_ORIENT_AUTO acts on it
     int sei_orient = 0;
+    // what the stream signals of its colour: colour_primaries, transfer_characteristics, matrix_coefficients and the
+    // full-range flag of the SPS's VUI video_signal_type, or the nclx colr property of a HEIF file, which wins (2, 2, 2,
+    // 0 where nothing is signalled).  Only H2J_COLOUR_AUTO acts on the last two; the first two are reported
+    int colour[4] = {2, 2, 2, 0};
     // the item's outputs, one per rendition it asks for (a plain item: one), resolved by the engine after
     // the parse from the rendition's options and the parsed size (resolve_output), or that rendition's own
     // error (invalid options fail it alone).  A job that did not parse has none
@@ -57,6 +61,11 @@ struct FrameJob {
         // has pad 0: it is the one without the option
         int pad = 0, box_w = 0, box_h = 0, pad_x = 0, pad_y = 0;
         uint8_t fill[3] = {0, 0, 0};
+        // colour (include/h2j.h "Colour"): 0: the planes as decoded; else H2J_COLOUR_EXPLICIT | matrix << 1 | full, the
+        // resolved source K3v normalises to JFIF's -- an output whose source is BT.601 full range has 0: it is the one
+        // without the option.  col_matrix (1, 6, 9; 0 without the option) and col_full: what the option resolved to
+        int colour = 0, col_matrix = 0, col_full = 0;
+        int32_t col_k[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // with colour != 0: K3v's constants (h2j_colour.k)
         // the luma size of the output's picture part (all of it without pad; the scale stage sizes from it): the
         // window's at the resolved scale, or the fit size
         int out_w() const { return scale_log2 == H2J_SCALE_RESAMPLE ? fit_w : h2j_scaled_dim(win_w, scale_log2); }
@@ -85,6 +94,8 @@ struct FrameJob {
         reorder_delay = false;
         field_pair = false;
         sei_orient = 0;
+        colour[0] = colour[1] = colour[2] = 2;
+        colour[3] = 0;
         nouts = 0;
     }
 };
@@ -106,5 +117,11 @@ int hevc_parse_grid(const uint8_t* const* tiles, const size_t* sizes, int rows, 
 // imir become job.sei_orient.  heif_orientation: that orientation alone (0, 2..8; negative: the demuxer's status)
 int heif_parse_picture(const uint8_t* data, size_t size, FrameJob& job);
 int heif_orientation(const uint8_t* data, size_t size);
+// What a stream signals of its colour without decoding it (FrameJob::colour): the first SPS that parses of an Annex-B
+// stream (false: none does); a HEIF file's nclx colr property, else its item's SPS (a negative status: the demuxer's, or
+// -100 for an item without an SPS)
+bool hevc_stream_colour(const uint8_t* data, size_t size, int* colour);
+bool h264_stream_colour(const uint8_t* data, size_t size, int* colour);
+int heif_stream_colour(const uint8_t* data, size_t size, int* colour);
 
 }  // namespace h2j

@@ -24,28 +24,38 @@ h2j_out_opts6 to_opts6(const h2j_out_opts5& o) {
                          o.qscale, o.sharpen, 0, {o.reserved[0] | o.reserved[1], o.reserved[2], o.reserved[3]}};
 }
 
-const h2j_out_opts7 kPlainOutput7 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, {0}};
-// (pad and background took over reserved[0..1] of h2j_out_opts6)
-h2j_out_opts7 widen7(const h2j_out_opts6& o) {
-    return h2j_out_opts7{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
-                         o.qscale, o.sharpen, o.format, 0, 0, {o.reserved[0] | o.reserved[1] | o.reserved[2]}};
+const h2j_out_opts8 kPlainOutput8 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+// (pad, background and colour took over reserved[0..2] of h2j_out_opts6, colour reserved[0] of h2j_out_opts7)
+h2j_out_opts8 widen8(const h2j_out_opts6& o) {
+    return h2j_out_opts8{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
+                         o.qscale, o.sharpen, o.format, 0, 0, (o.reserved[0] | o.reserved[1] | o.reserved[2]) ? kColourReserved : 0};
+}
+h2j_out_opts8 widen8(const h2j_out_opts7& o) {
+    return h2j_out_opts8{o.scale_log2, o.max_dim, o.fit_w, o.fit_h, o.flags, o.crop_x, o.crop_y, o.crop_w, o.crop_h, o.orient,
+                         o.qscale, o.sharpen, o.format, o.pad, o.background, o.reserved[0] ? kColourReserved : 0};
 }
 
 bool reserved_zero(const h2j_out_opts6& o) { return std::all_of(o.reserved, o.reserved + 3, [](int32_t r) { return r == 0; }); }
-bool reserved_zero(const h2j_out_opts7& o) { return o.reserved[0] == 0; }
+bool reserved_zero(const h2j_out_opts8& o) { return o.colour != kColourReserved; }
+// colour (include/h2j.h "Colour"): off, the stream's, or a source the caller names
+bool colour_valid(const h2j_out_opts8& o) {
+    if (o.colour == 0 || o.colour == H2J_COLOUR_AUTO) return true;
+    const int mc = (o.colour & 0xFF) >> 1;
+    return (o.colour & ~0xFF) == H2J_COLOUR_EXPLICIT && (mc == 1 || mc == 5 || mc == 6 || mc == 9);
+}
 // padded output (include/h2j.h "Padded output"): a two-sided box to pad to, a 24-bit colour, and no colour without pad
-bool pad_valid(const h2j_out_opts7& o) {
+bool pad_valid(const h2j_out_opts8& o) {
     if (o.pad < 0 || o.pad > 1 || (o.background & ~0xFFFFFF)) return false;
     if (!o.pad) return o.background == 0;
     // (the canvas is the caller's number, not the picture's: H2J_PAD_MAX_SAMPLES bounds its memory and its int32 offsets)
     return o.fit_w >= 2 && o.fit_h >= 2 && static_cast<int64_t>(2 * (o.fit_w / 2)) * (2 * (o.fit_h / 2)) <= H2J_PAD_MAX_SAMPLES;
 }
 // finishing (include/h2j.h "Finishing"): a fixed quantiser scale, an unsharp mask
-bool finish_valid(const h2j_out_opts7& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
+bool finish_valid(const h2j_out_opts8& o) { return (o.qscale == 0 || (o.qscale >= 2 && o.qscale <= 31)) && o.sharpen >= 0 && o.sharpen <= 64; }
 // RGB output (include/h2j.h "RGB output"): a known format, and no quantiser scale for pixels
-bool format_valid(const h2j_out_opts7& o) { return o.format >= H2J_FMT_JPEG && o.format <= H2J_FMT_RGB8_PLANAR && !(o.format && o.qscale); }
+bool format_valid(const h2j_out_opts8& o) { return o.format >= H2J_FMT_JPEG && o.format <= H2J_FMT_RGB8_PLANAR && !(o.format && o.qscale); }
 // the orientation (0, 2..8) the options name for a picture whose display orientation SEI says sei_orient
-int resolve_orient(const h2j_out_opts7& o, int sei_orient) {
+int resolve_orient(const h2j_out_opts8& o, int sei_orient) {
     const int r = o.orient == H2J_ORIENT_AUTO ? sei_orient : o.orient;
     return r == 1 ? 0 : r;
 }
@@ -58,9 +68,9 @@ bool fit_valid(int fit_w, int fit_h, int flags) {
 }
 // what can be said of the options before the picture's size is known (an item none of whose renditions
 // passes is not parsed); the window's place in the picture is checked by resolve_output
-bool out_opts_valid(const h2j_out_opts7& o) {
+bool out_opts_valid(const h2j_out_opts8& o) {
     if (o.scale_log2 < 0 || o.scale_log2 > 3 || o.max_dim < 0) return false;
-    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o) || !format_valid(o) || !pad_valid(o)) return false;
+    if (!reserved_zero(o) || o.orient < H2J_ORIENT_AUTO || o.orient > 8 || !finish_valid(o) || !format_valid(o) || !pad_valid(o) || !colour_valid(o)) return false;
     if (o.crop_x < 0 || o.crop_y < 0 || o.crop_w < 0 || o.crop_h < 0 || ((o.crop_x | o.crop_y | o.crop_w | o.crop_h) & 1)) return false;
     if (o.flags & H2J_FIT_COVER) {  // a box, and nothing else that sizes the output
         if (o.flags != H2J_FIT_COVER || o.fit_w < 2 || o.fit_h < 2 || o.scale_log2 || o.max_dim) return false;
@@ -69,7 +79,7 @@ bool out_opts_valid(const h2j_out_opts7& o) {
     if (!fit_valid(o.fit_w, o.fit_h, o.flags)) return false;
     return !((o.fit_w || o.fit_h) && (o.scale_log2 || o.max_dim));
 }
-int resolve_scale(const h2j_out_opts7& o, int w, int h) {
+int resolve_scale(const h2j_out_opts8& o, int w, int h) {
     int k = o.scale_log2;
     if (o.max_dim > 0)
         while (k < 3 && std::max(h2j_scaled_dim(w, k), h2j_scaled_dim(h, k)) > o.max_dim) k++;
@@ -82,7 +92,7 @@ int resolve_scale(const h2j_out_opts7& o, int w, int h) {
 // resampler's arithmetic reduces to K3s's there) is the scaled output of that k; K3r gets the rest.
 // Orientation (include/h2j.h "Orientation"; sei_orient: the picture's, for H2J_ORIENT_AUTO) comes first: the
 // rule runs on the oriented size, the window is in the oriented picture
-static FrameJob::Output resolve_picture(const h2j_out_opts7& o, int W, int H, int sei_orient) {
+static FrameJob::Output resolve_picture(const h2j_out_opts8& o, int W, int H, int sei_orient) {
     FrameJob::Output out;
     out.qscale = o.qscale;
     out.sharpen = o.sharpen;
@@ -127,9 +137,20 @@ static FrameJob::Output resolve_picture(const h2j_out_opts7& o, int W, int H, in
 }
 // ... and the padding (include/h2j.h "Padded output") last: the picture part is what the options without pad resolve
 // to, centred in the canvas the way cover centres its window; a picture part that fills the canvas is not padded
-FrameJob::Output resolve_output(const h2j_out_opts7& o, int W, int H, int sei_orient) {
+// The colour (include/h2j.h "Colour") is resolved with the picture: a source that is JFIF's already (BT.601, full range)
+// leaves the output the one without the option
+FrameJob::Output resolve_output(const h2j_out_opts8& o, int W, int H, int sei_orient, const int* stream_colour) {
     FrameJob::Output out = resolve_picture(o, W, H, sei_orient);
-    if (out.error || !o.pad) return out;
+    if (out.error) return out;
+    if (o.colour) {
+        if (resolve_colour(o, stream_colour, &out.col_matrix, &out.col_full)) {
+            out.error = H2J_ERR_OUT_OPTS;
+            return out;
+        }
+        out.colour = (out.col_matrix == 6 && out.col_full) ? 0 : (H2J_COLOUR_EXPLICIT | out.col_matrix << 1 | out.col_full);
+        if (out.colour) colour_coeffs(out.col_matrix, out.col_full, out.col_k);
+    }
+    if (!o.pad) return out;
     const int bw = 2 * (o.fit_w / 2), bh = 2 * (o.fit_h / 2), ow = out.out_w(), oh = out.out_h();
     if (ow == bw && oh == bh) return out;
     int ycc[3] = {0, 128, 128};
@@ -142,6 +163,82 @@ FrameJob::Output resolve_output(const h2j_out_opts7& o, int W, int H, int sei_or
     for (int c = 0; c < 3; c++) out.fill[c] = static_cast<uint8_t>(ycc[c]);
     return out;
 }
+int resolve_colour(const h2j_out_opts8& o, const int* stream_colour, int* matrix, int* full) {
+    int mc = 6, fr = 1;
+    if (o.colour == H2J_COLOUR_AUTO) {
+        mc = stream_colour ? stream_colour[2] : 2;
+        fr = (stream_colour && stream_colour[3]) ? 1 : 0;  // (no range signalled: limited, E.2.1)
+        if (mc == 2) mc = 6;  // unspecified: how the library reads such streams without the option
+    } else if (o.colour != 0) {
+        mc = (o.colour & 0xFF) >> 1;
+        fr = o.colour & 1;
+    }
+    *matrix = mc == 5 ? 6 : mc;
+    *full = fr;
+    return (colour_valid(o) && (mc == 1 || mc == 5 || mc == 6 || mc == 9)) ? 0 : H2J_ERR_OUT_OPTS;
+}
+
+namespace {
+// exact rationals on 128-bit integers (the terms below stay far inside them: denominators are products of a few
+// four-digit numbers)
+typedef __int128 I128;
+struct Q {
+    I128 n, d;  // d > 0, reduced
+};
+I128 gcd128(I128 a, I128 b) {
+    if (a < 0) a = -a;
+    while (b) {
+        const I128 t = a % b;
+        a = b;
+        b = t;
+    }
+    return a ? a : 1;
+}
+Q mk(I128 n, I128 d) {
+    if (d < 0) {
+        n = -n;
+        d = -d;
+    }
+    const I128 g = gcd128(n, d);
+    return Q{n / g, d / g};
+}
+Q operator-(Q a, Q b) { return mk(a.n * b.d - b.n * a.d, a.d * b.d); }
+Q operator*(Q a, Q b) { return mk(a.n * b.n, a.d * b.d); }
+Q operator/(Q a, Q b) { return mk(a.n * b.d, a.d * b.n); }
+// rnd(q 2^sh): to nearest, halves away from zero
+int32_t rnd_shift(Q q, int sh) {
+    const bool neg = q.n < 0;
+    const I128 n = (neg ? -q.n : q.n) << sh;
+    const I128 r = (2 * n + q.d) / (2 * q.d);
+    return static_cast<int32_t>(neg ? -r : r);
+}
+}  // namespace
+
+int colour_coeffs(int matrix, int full, int32_t* k) {
+    if (!k || (full != 0 && full != 1) || !(matrix == 1 || matrix == 5 || matrix == 6 || matrix == 9)) return H2J_ERR_OUT_OPTS;
+    const Q one = mk(1, 1), two = mk(2, 1);
+    const Q Kr = matrix == 1 ? mk(2126, 10000) : matrix == 9 ? mk(2627, 10000) : mk(299, 1000);
+    const Q Kb = matrix == 1 ? mk(722, 10000) : matrix == 9 ? mk(593, 10000) : mk(114, 1000);
+    const Q Kg = one - Kr - Kb;
+    const Q Krt = mk(299, 1000), Kbt = mk(114, 1000), Kgt = mk(587, 1000);  // the target: JFIF's
+    const Q a = two * Kbt * (one - Kb) - two * Kgt * Kb * (one - Kb) / Kg;
+    const Q b = two * Krt * (one - Kr) - two * Kgt * Kr * (one - Kr) / Kg;
+    const Q c = (two * (one - Kb) - a) / (two * (one - Kbt));
+    const Q d = (mk(0, 1) - b) / (two * (one - Kbt));
+    const Q e = (mk(0, 1) - a) / (two * (one - Krt));
+    const Q f = (two * (one - Kr) - b) / (two * (one - Krt));
+    const Q g = mk(255, full ? 255 : 224);
+    k[0] = full ? 0 : 16;
+    k[1] = rnd_shift(mk(255, full ? 255 : 219), 20);
+    k[2] = rnd_shift(a * g, 16);
+    k[3] = rnd_shift(b * g, 16);
+    k[4] = rnd_shift(c * g, 16);
+    k[5] = rnd_shift(d * g, 16);
+    k[6] = rnd_shift(e * g, 16);
+    k[7] = rnd_shift(f * g, 16);
+    return 0;
+}
+
 int pad_colour(uint32_t rgb, int* ycc) {
     if (!ycc || (rgb & ~0xFFFFFFu)) return H2J_ERR_OUT_OPTS;
     const int r = static_cast<int>(rgb >> 16), g = static_cast<int>((rgb >> 8) & 255), b = static_cast<int>(rgb & 255);
@@ -154,7 +251,7 @@ int pad_colour(uint32_t rgb, int* ycc) {
 }
 // W, H: the parsed picture's cropped size (0: not parsed).  Options without a window or cover get the
 // message they always got
-std::string out_opts_message(const h2j_out_opts7& o, int W, int H, int sei_orient) {
+std::string out_opts_message(const h2j_out_opts8& o, int W, int H, int sei_orient, const int* stream_colour) {
     std::string m = "invalid output options: scale_log2 " + std::to_string(o.scale_log2) + " (0..3), max_dim " +
            std::to_string(o.max_dim) + " (>= 0), fit " + std::to_string(o.fit_w) + " x " + std::to_string(o.fit_h) +
            " (0 or 2..65535, not with scale_log2 / max_dim), flags " + std::to_string(o.flags) +
@@ -170,6 +267,12 @@ std::string out_opts_message(const h2j_out_opts7& o, int W, int H, int sei_orien
     if (o.pad != 0 || o.background != 0)
         m += "; pad " + std::to_string(o.pad) + " (0..1; needs a box: fit or cover with both sides, of at most " + std::to_string(H2J_PAD_MAX_SAMPLES) + " samples), background " + std::to_string(o.background) +
              " (0x00RRGGBB, 0 without pad)";
+    if (o.colour != 0 && o.colour != kColourReserved) {
+        m += "; colour " + std::to_string(o.colour) + " (0, -1: the stream's, or 256 | matrix_coefficients << 1 | full range with matrix_coefficients 1, 5, 6 or 9)";
+        int mc = 0, fr = 0;
+        if (o.colour == H2J_COLOUR_AUTO && W > 0 && H > 0 && resolve_colour(o, stream_colour, &mc, &fr))
+            m += "; the stream signals matrix_coefficients " + std::to_string(mc) + ", which is not converted (1, 5, 6, 9 and 2 are)";
+    }
     if (!(window && W > 0 && H > 0)) return m;
     const int ro = (o.orient >= H2J_ORIENT_AUTO && o.orient <= 8) ? resolve_orient(o, sei_orient) : 0;
     if (ro >= 5) std::swap(W, H);
@@ -180,12 +283,18 @@ std::string out_opts_message(const h2j_out_opts7& o, int W, int H, int sei_orien
 
 int crop_window6(int w, int h, const h2j_out_opts6* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient) {
     if (!o) return H2J_ERR_OUT_OPTS;
-    const h2j_out_opts7 o7 = widen7(*o);  // (pad 0: the canvas is the picture part)
+    const h2j_out_opts8 o8 = widen8(*o);  // (pad 0: the canvas is the picture part)
     int32_t place[4];
-    return crop_window7(w, h, &o7, sei_orient, win, ow, oh, orient, place);
+    return crop_window8(w, h, &o8, sei_orient, win, ow, oh, orient, place);
 }
 
 int crop_window7(int w, int h, const h2j_out_opts7* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient, int32_t* place) {
+    if (!o) return H2J_ERR_OUT_OPTS;
+    const h2j_out_opts8 o8 = widen8(*o);
+    return crop_window8(w, h, &o8, sei_orient, win, ow, oh, orient, place);
+}
+
+int crop_window8(int w, int h, const h2j_out_opts8* o, int sei_orient, int32_t* win, int* ow, int* oh, int* orient, int32_t* place) {
     if (!o || !win || !ow || !oh || !orient || !place || w < 2 || h < 2 || w > 65536 || h > 65536 || ((w | h) & 1) || sei_orient < 0 ||
         sei_orient > 8 || !out_opts_valid(*o))
         return H2J_ERR_OUT_OPTS;

@@ -19,7 +19,10 @@ _LIB_NAME = "libH265ToJpeg.so"
 # the C entry points younger than libH265ToJpeg.so's fixed export list (csrc/host/api_ext.h): a thin library beside it
 _EXT_LIB_NAME = "libH265ToJpegExt.so"
 _EXT_SYMBOLS = ("h2j_engine_transcode_multi7", "h2j_engine_submit_multi7", "h2j_engine_decode_multi7",
-                "h2j_h265_to_jpeg_mem_multi7", "h2j_crop_window7", "h2j_pad_colour")
+                "h2j_h265_to_jpeg_mem_multi7", "h2j_crop_window7", "h2j_pad_colour",
+                # colour (an older build of the library beside an older host library lacks these: it still loads)
+                "h2j_engine_transcode_multi8", "h2j_engine_submit_multi8", "h2j_engine_decode_multi8",
+                "h2j_h265_to_jpeg_mem_multi8", "h2j_stream_colour", "h2j_colour_coeffs")
 _lib = None
 
 
@@ -79,6 +82,19 @@ class OutOpts7(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 1)]
 
 
+class OutOpts8(ctypes.Structure):
+    """include/h2j.h h2j_out_opts8: h2j_out_opts7 and the colour (the source matrix and range K3v normalises to JFIF's)."""
+    _fields_ = [("scale_log2", ctypes.c_int32), ("max_dim", ctypes.c_int32), ("fit_w", ctypes.c_int32),
+                ("fit_h", ctypes.c_int32), ("flags", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+                ("crop_y", ctypes.c_int32), ("crop_w", ctypes.c_int32), ("crop_h", ctypes.c_int32),
+                ("orient", ctypes.c_int32), ("qscale", ctypes.c_int32), ("sharpen", ctypes.c_int32),
+                ("format", ctypes.c_int32), ("pad", ctypes.c_int32), ("background", ctypes.c_int32),
+                ("colour", ctypes.c_int32)]
+
+
+COLOUR_AUTO, COLOUR_EXPLICIT = -1, 0x100  # include/h2j.h H2J_COLOUR_*
+COLOUR_MATRICES = {"bt709": 1, "bt601": 6, "bt2020": 9}  # the matrix_coefficients value of each name
+COLOUR_RANGES = {"limited": 0, "full": 1}
 FMT_JPEG, FMT_RGB8, FMT_RGB8_PLANAR = 0, 1, 2  # include/h2j.h H2J_FMT_*
 FORMATS = {"jpeg": FMT_JPEG, "rgb": FMT_RGB8, "rgb_planar": FMT_RGB8_PLANAR}  # the spec key "format"
 FIT_STRETCH = 1  # include/h2j.h H2J_FIT_STRETCH
@@ -253,7 +269,8 @@ def load_library() -> ctypes.CDLL:
     if os.path.exists(ext_path):
         ext = ctypes.CDLL(ext_path, mode=ctypes.RTLD_GLOBAL)
         for sym in _EXT_SYMBOLS:
-            setattr(lib, sym, getattr(ext, sym))
+            if hasattr(ext, sym):
+                setattr(lib, sym, getattr(ext, sym))
     if hasattr(lib, "h2j_engine_transcode_multi7"):
         opt7p = ctypes.POINTER(OutOpts7)
         i32p = ctypes.POINTER(ctypes.c_int32)
@@ -273,6 +290,24 @@ def load_library() -> ctypes.CDLL:
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32p]
         lib.h2j_pad_colour.restype = ctypes.c_int
         lib.h2j_pad_colour.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "h2j_engine_transcode_multi8"):  # colour
+        opt8p = ctypes.POINTER(OutOpts8)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lib.h2j_engine_transcode_multi8.restype = ctypes.c_int
+        lib.h2j_engine_transcode_multi8.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(u8p), szp, i32p, opt8p, u8p,
+                                                    ctypes.c_size_t, szp, szp, ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_engine_submit_multi8.restype = ctypes.c_int64
+        lib.h2j_engine_submit_multi8.argtypes = lib.h2j_engine_transcode_multi8.argtypes
+        lib.h2j_engine_decode_multi8.restype = ctypes.c_int
+        lib.h2j_engine_decode_multi8.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.c_int, opt8p, ctypes.c_int,
+                                                 u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        lib.h2j_h265_to_jpeg_mem_multi8.restype = ctypes.c_int
+        lib.h2j_h265_to_jpeg_mem_multi8.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, opt8p, ctypes.POINTER(u8p), szp,
+                                                    ctypes.POINTER(ctypes.c_int), i32p]
+        lib.h2j_stream_colour.restype = ctypes.c_int
+        lib.h2j_stream_colour.argtypes = [u8p, ctypes.c_size_t, i32p]
+        lib.h2j_colour_coeffs.restype = ctypes.c_int
+        lib.h2j_colour_coeffs.argtypes = [ctypes.c_int, ctypes.c_int, i32p]
     lib.h2j_free.argtypes = [ctypes.c_void_p]
     lib.h2j_engine_wait.restype = ctypes.c_int
     lib.h2j_engine_wait.argtypes = [ctypes.c_void_p, ctypes.c_int64]
@@ -306,6 +341,7 @@ STAT_KEYS = ["parse_ms", "h2d_ms", "recon_ms", "deblock_ms", "sao_ms", "jpeg_ms"
              "payload_copied_bytes", "scale_ms", "renditions", "parsed", "raw_bytes"]
 # the entries of h2j_engine_stats behind those (a kernel or host library older than them leaves them 0)
 STAT_KEYS_LATER = ["pad_bytes"]
+STAT_KEYS_COLOUR = ["colour_bytes"]  # ... and behind that one
 
 
 def _per_item(v, n, name):
@@ -362,7 +398,26 @@ def _out_opts(scale, max_dim, n, fit=None, stretch=False):
                             for a, b, (w, h), t in zip(sc, md, ft, stf)])
 
 
-_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen", "format", "pad")
+_SPEC_KEYS = ("scale", "max_dim", "fit", "stretch", "crop", "cover", "orient", "qscale", "sharpen", "format", "pad", "colour")
+
+
+def _is_colour_source(v):
+    """A named source: a (matrix, range) pair of strings, the first a matrix's name (so a per-item sequence of two
+    "auto" is not one)."""
+    return isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(x, str) for x in v) and v[0] in COLOUR_MATRICES
+
+
+def _colour_value(v, what):
+    """A colour as h2j_out_opts8 takes it: None or False: 0 (off); "auto": H2J_COLOUR_AUTO, the stream's signalling; a
+    (matrix, range) pair -- "bt601" / "bt709" / "bt2020", "limited" / "full" -- the source the caller names:
+    H2J_COLOUR_EXPLICIT | matrix_coefficients << 1 | full."""
+    if v is None or v is False:
+        return 0
+    if isinstance(v, str) and v == "auto":
+        return COLOUR_AUTO
+    if _is_colour_source(v) and v[0] in COLOUR_MATRICES and v[1] in COLOUR_RANGES:
+        return COLOUR_EXPLICIT | COLOUR_MATRICES[v[0]] << 1 | COLOUR_RANGES[v[1]]
+    raise ValueError(f"{what}: colour {v!r} is not \"auto\" or a (matrix, range) pair of {sorted(COLOUR_MATRICES)} and {sorted(COLOUR_RANGES)}")
 
 
 def _is_colour(v):
@@ -423,7 +478,8 @@ def rendition_spec(spec):
     key those and orient: the fields of h2j_out_opts4; with a qscale or sharpen key those (orient 0 if the spec
     names none), qscale and sharpen: the fields of h2j_out_opts5; with a format key those (0 where the spec names
     none) and format: the fields of h2j_out_opts6; with a pad key those (0 where the spec names none), pad and
-    background: the fields of h2j_out_opts7.
+    background: the fields of h2j_out_opts7; with a colour key those (0 where the spec names none) and colour: the
+    fields of h2j_out_opts8.
 
     A spec is an int (scale), a (w, h) pair (fit; 0 or None: no bound on that axis) or a dict with any
     of scale, max_dim, fit, stretch, crop (an (x, y, w, h) window in luma samples of the picture; w, h 0:
@@ -435,7 +491,10 @@ def rendition_spec(spec):
     0: none) and format ("jpeg": the file, as without the key; "rgb": the rendition's final picture as 8-bit RGB
     pixels, numpy (H, W, 3); "rgb_planar": the same as (3, H, W) -- converted on the GPU, no JPEG loss) and pad (True,
     or an (r, g, b) colour: the rendition letterboxed to the exact size of its box -- a two-sided fit, or a cover -- the
-    picture part centred, the rest black or that colour; the rendition then has the box's size whatever the picture's).
+    picture part centred, the rest black or that colour; the rendition then has the box's size whatever the picture's)
+    and colour ("auto", or a (matrix, range) pair such as ("bt709", "limited"): the rendition's planes converted on the
+    GPU from that source matrix and range -- "auto": what the stream signals -- to JFIF's BT.601 full range, which every
+    JPEG and RGB array is read as).
     Values are not range-checked here: the engine fails a rendition
     with invalid options alone (ERR_OUT_OPTS)."""
     if isinstance(spec, (bool, np.bool_)):
@@ -447,7 +506,11 @@ def rendition_spec(spec):
     if isinstance(spec, dict):
         bad = [k for k in spec if k not in _SPEC_KEYS]
         if bad:
-            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad)")
+            raise ValueError(f"rendition {spec!r}: unknown key {bad[0]!r} (scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad, colour)")
+        if "colour" in spec:  # the h2j_out_opts8 fields, whatever else the spec names
+            rest = dict(spec)
+            col = _colour_value(rest.pop("colour"), f"rendition {spec!r}")
+            return (tuple(rendition_spec(rest)) + (0,) * 10)[:15] + (col,)
         if "pad" in spec:  # the h2j_out_opts7 fields, whatever else the spec names
             rest = dict(spec)
             pad = _pad_value(rest.pop("pad"), f"rendition {spec!r}")
@@ -541,7 +604,9 @@ def _multi_opts(per_item):
     n = len(per_item)
     nrend = (ctypes.c_int32 * n)(*[len(x) for x in per_item])
     flat = [t for x in per_item for t in x]
-    if any(len(t) > 13 for t in flat):  # a padding: the multi7 calls
+    if any(len(t) > 15 for t in flat):  # a colour: the multi8 calls
+        opts = (OutOpts8 * len(flat))(*[OutOpts8(*(tuple(t) + (0,) * 11)[:16]) for t in flat])
+    elif any(len(t) > 13 for t in flat):  # a padding: the multi7 calls
         opts = (OutOpts7 * len(flat))(*[OutOpts7(*(tuple(t) + (0,) * 10)[:15]) for t in flat])
     elif any(len(t) > 12 for t in flat):  # a format: the multi6 calls
         opts = (OutOpts6 * len(flat))(*[OutOpts6(*(tuple(t) + (0,) * 8)[:13]) for t in flat])
@@ -615,8 +680,18 @@ def _per_item_pad(v, n):
     return v
 
 
-def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None, format=None, pad=None):
-    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale, sharpen, format or pad is given."""
+def _per_item_colour(v, n):
+    """colour (None, "auto" or one (matrix, range) pair for every item, or a per-item sequence of those) -> n values."""
+    if v is None or v is False or isinstance(v, str) or _is_colour_source(v):
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"colour: {len(v)} entries for {n} streams")
+    return v
+
+
+def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qscale=None, sharpen=None, format=None, pad=None, colour=None):
+    """Per-item rendition dicts of transcode()'s keywords when crop, cover, orient, qscale, sharpen, format, pad or colour is given."""
     sc, md = _per_item(scale, n, "scale"), _per_item(max_dim, n, "max_dim")
     ft = [None] * n if fit is None else _per_item_fit(fit, n)
     if isinstance(stretch, (bool, np.bool_)) or stretch is None:
@@ -631,6 +706,7 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
     qs, sh = _per_item_finish(qscale, n, "qscale"), _per_item_finish(sharpen, n, "sharpen")
     fm = _per_item_format(format, n)
     pd = _per_item_pad(pad, n)
+    cl = _per_item_colour(colour, n)
     out = []
     for i in range(n):
         d = {"scale": sc[i], "max_dim": md[i], "stretch": stf[i]}
@@ -650,6 +726,8 @@ def _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient=None, qsc
             d["format"] = fm[i]
         if pd[i] is not None and pd[i] is not False:
             d["pad"] = pd[i]
+        if cl[i] is not None and cl[i] is not False:
+            d["colour"] = cl[i]
         out.append([d])
     return out
 
@@ -700,6 +778,29 @@ def stream_orientation(stream: bytes) -> int:
     return r
 
 
+def stream_colour(stream: bytes) -> dict:
+    """What a stream signals of its colour, without decoding it (include/h2j_ext.h h2j_stream_colour; no GPU):
+    {"primaries", "transfer", "matrix", "full_range"} -- colour_primaries, transfer_characteristics and
+    matrix_coefficients as the specs number them, from the SPS's VUI or, in a HEIF file, the nclx colour property, which
+    wins; 2, 2, 2 and False where nothing is signalled.  colour="auto" acts on the last two.  ValueError for bytes that
+    are no stream."""
+    info = (ctypes.c_int32 * 4)()
+    r = load_library().h2j_stream_colour(_u8(stream), len(stream), info)
+    if r < 0:
+        raise ValueError(f"h2j_stream_colour failed ({r}): not an H.264/H.265 Annex-B stream or a HEIF file the library reads")
+    return {"primaries": int(info[0]), "transfer": int(info[1]), "matrix": int(info[2]), "full_range": bool(info[3])}
+
+
+def colour_coeffs(matrix, full) -> tuple:
+    """(oy, LY, LB, LR, CB, CR, RB, RR): K3v's constants for a source matrix ("bt601" / "bt709" / "bt2020", or a
+    matrix_coefficients value 1, 5, 6, 9) and range (include/h2j_ext.h h2j_colour_coeffs)."""
+    k = (ctypes.c_int32 * 8)()
+    rc = load_library().h2j_colour_coeffs(int(COLOUR_MATRICES.get(matrix, matrix)), int(bool(full)), k)
+    if rc != 0:
+        raise ValueError(f"h2j_colour_coeffs({matrix!r}, {full!r}) failed ({rc})")
+    return tuple(int(x) for x in k)
+
+
 def fit_size(w: int, h: int, fit, stretch: bool = False):
     """(W_o, H_o): the output size of a cropped w x h picture for fit=(fit_w, fit_h) (0 or None: no
     bound on that axis) -- include/h2j.h h2j_fit_size, the one place the size rule lives."""
@@ -747,7 +848,8 @@ class Engine:
         return {"threads": arr[0], "numa_node": arr[1], "pinned_cpus": arr[2], "first_cpu": arr[3]}
 
     def transcode(self, streams: Sequence[bytes], scale=None, max_dim=None, fit=None,
-                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None, pad=None) -> List[Optional[bytes]]:
+                  stretch=False, crop=None, cover=None, orient=None, qscale=None, sharpen=None, format=None, pad=None,
+                  colour=None) -> List[Optional[bytes]]:
         """Annex-B H.264/H.265 stills -> JPEG bytes (None for items that failed).
 
         scale (0..3: the JPEG at 1/1, 1/2, 1/4, 1/8 of the decoded size) and max_dim (> 0: the
@@ -778,12 +880,16 @@ class Engine:
 
         pad (True: black, or an (r, g, b) tuple; h2j_out_opts7): one value for every item or a per-item sequence of
         values or None; the item is letterboxed to the exact size of its box (a two-sided fit, or a cover), so
-        transcode(streams, fit=(224, 224), pad=True, format="rgb_planar") returns arrays of one shape, (3, 224, 224)."""
+        transcode(streams, fit=(224, 224), pad=True, format="rgb_planar") returns arrays of one shape, (3, 224, 224).
+
+        colour ("auto", or a (matrix, range) pair such as ("bt709", "limited"); h2j_out_opts8): one value for every item
+        or a per-item sequence of values or None; the item's planes are converted from that source -- "auto": what the
+        stream signals (stream_colour) -- to JFIF's BT.601 full range before anything else finishes them."""
         n = len(streams)
         if n == 0:
             return []
-        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format, pad)):  # one rendition per item through the multi3 .. multi7 call
-            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad))
+        if any(v is not None for v in (crop, cover, orient, qscale, sharpen, format, pad, colour)):  # one rendition per item through the multi3 .. multi8 call
+            out = self.transcode_multi(streams, _window_specs(n, scale, max_dim, fit, stretch, crop, cover, orient, qscale, sharpen, format, pad, colour))
             self.last_status = [st[0] for st in self.last_status]
             return [o[0] for o in out]
         opts = _out_opts(scale, max_dim, n, fit, stretch)
@@ -818,7 +924,7 @@ class Engine:
 
         renditions: one list of specs for every item, or one such list per item (normalize_renditions);
         a spec is an int (scale), a (w, h) tuple (fit) or a dict with any of scale, max_dim, fit,
-        stretch, crop, cover, orient, qscale, sharpen, format, pad (rendition_spec).  The entry of a raw rendition (format "rgb" /
+        stretch, crop, cover, orient, qscale, sharpen, format, pad, colour (rendition_spec).  The entry of a raw rendition (format "rgb" /
         "rgb_planar") is a numpy uint8 array, (H, W, 3) / (3, H, W).  last_status has the result's shape.  out_cap: the
         output buffer size tried first (0: an estimate); renditions that did not fit (-50) make the call retry with a
         larger one -- raw renditions are then sized exactly, from the sizes the first pass reported."""
@@ -838,11 +944,11 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
         cap = int(out_cap) or _multi_cap(streams, per_item, 1 << 20)
         offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
-        wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7) else None  # the multi6 / multi7 calls report the sizes
+        wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7, OutOpts8) else None  # the multi6 / multi7 calls report the sizes
         jpeg_cap = cap
         for _ in range(4):  # on -50 (output buffer too small) retry larger, as transcode()
             out = (ctypes.c_uint8 * cap)()
-            call = {OutOpts7: "h2j_engine_transcode_multi7", OutOpts6: "h2j_engine_transcode_multi6", OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
+            call = {OutOpts8: "h2j_engine_transcode_multi8", OutOpts7: "h2j_engine_transcode_multi7", OutOpts6: "h2j_engine_transcode_multi6", OutOpts5: "h2j_engine_transcode_multi5", OutOpts4: "h2j_engine_transcode_multi4", OutOpts3: "h2j_engine_transcode_multi3"}.get(opts._type_, "h2j_engine_transcode_multi")
             call = getattr(self._lib, call)
             rc = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
             small = [i for i in range(total) if status[i] == -50]
@@ -901,9 +1007,9 @@ class Engine:
             cap = _multi_cap(streams, per_item, 2 << 20)
             out = (ctypes.c_uint8 * cap)()
             offs, lens, status = (ctypes.c_size_t * total)(), (ctypes.c_size_t * total)(), (ctypes.c_int * total)()
-            wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7) else None
+            wh = (ctypes.c_int32 * (2 * total))() if opts._type_ in (OutOpts6, OutOpts7, OutOpts8) else None
             held.append((bufs, ptrs, sizes, nrend, opts, out, offs, lens, status, per_item, wh))
-            call = {OutOpts7: "h2j_engine_submit_multi7", OutOpts6: "h2j_engine_submit_multi6", OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
+            call = {OutOpts8: "h2j_engine_submit_multi8", OutOpts7: "h2j_engine_submit_multi7", OutOpts6: "h2j_engine_submit_multi6", OutOpts5: "h2j_engine_submit_multi5", OutOpts4: "h2j_engine_submit_multi4", OutOpts3: "h2j_engine_submit_multi3"}.get(opts._type_, "h2j_engine_submit_multi")
             call = getattr(self._lib, call)
             t = call(self._h, n, ptrs, sizes, nrend, opts, out, cap, offs, lens, status, *(() if wh is None else (wh,)))
             if t <= 0:
@@ -944,6 +1050,8 @@ class Engine:
         Renditions with a crop or cover key go through decode_multi3, with an orient key through decode_multi4,
         with a qscale or sharpen key through decode_multi5, with a pad key through decode_multi7."""
         specs = normalize_renditions([list(renditions)], 1)[0]
+        if any(len(t) > 15 for t in specs):
+            return self.decode_multi8(stream, renditions, pick)[:5]
         if any(len(t) > 13 for t in specs):
             return self.decode_multi7(stream, renditions, pick)[:5]
         if any(len(t) > 10 for t in specs):
@@ -1041,6 +1149,27 @@ class Engine:
         return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
                 int(info[8]), int(info[9]), int(info[10]), int(info[11]), int(info[12]),
                 tuple(int(info[i]) for i in range(13, 17)), (info[17] & 255, (info[17] >> 8) & 255, (info[17] >> 16) & 255))
+
+    def decode_multi8(self, stream: bytes, renditions, pick: int):
+        """decode_multi through h2j_engine_decode_multi8 (colour): decode_multi7's result, then the resolved source
+        matrix (matrix_coefficients 1, 6 or 9; 0 with colour off), the resolved range (1 full, 0 limited) and whether the
+        rendition was converted (0: colour off, or BT.601 full range).  The planes are what K4 reads."""
+        specs = normalize_renditions([list(renditions)], 1)[0]
+        total = len(specs)
+        opts = (OutOpts8 * total)(*[OutOpts8(*(tuple(t) + (0,) * 11)[:16]) for t in specs])
+        buf = _u8(stream)
+        cap = 8192 * 8192 * 3 // 2
+        out = np.zeros(cap, dtype=np.uint8)
+        info = (ctypes.c_int * 21)()
+        rc = self._lib.h2j_engine_decode_multi8(self._h, buf, len(stream), total, opts, int(pick),
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, info)
+        if rc < 0:
+            raise RuntimeError(f"h2j_engine_decode_multi8 failed ({rc}): {self.error()}")
+        y, u, v, _ = self._planes(out, info)
+        return (y, u, v, (int(info[0]), int(info[1])), int(info[2]), tuple(int(info[i]) for i in range(4, 8)),
+                int(info[8]), int(info[9]), int(info[10]), int(info[11]), int(info[12]),
+                tuple(int(info[i]) for i in range(13, 17)), (info[17] & 255, (info[17] >> 8) & 255, (info[17] >> 16) & 255),
+                int(info[18]), int(info[19]), int(info[20]))
 
     def transcode_raw(self, ptrs, sizes, n, out, cap, offs, lens, status) -> int:
         """Zero-copy variant for benchmarks (pre-built ctypes arrays)."""
@@ -1217,7 +1346,7 @@ class Engine:
         return [(int(arr[3 * i]), arr[3 * i + 1], arr[3 * i + 2]) for i in range(min(n, cap))]
 
     def stats(self) -> dict:
-        keys = STAT_KEYS + STAT_KEYS_LATER
+        keys = STAT_KEYS + STAT_KEYS_LATER + STAT_KEYS_COLOUR
         arr = (ctypes.c_double * len(keys))()
         self._lib.h2j_engine_stats(self._h, arr, len(keys))
         return {k: arr[i] for i, k in enumerate(keys)}

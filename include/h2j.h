@@ -376,6 +376,60 @@ typedef struct {
     int32_t reserved[1];                              /* must be 0 */
 } h2j_out_opts7;                                      /* 64 bytes */
 
+/* Colour: a rendition's planes normalised to JFIF's matrix and range (DESIGN.md "Colour (K3v)").
+ * Without the option every JPEG and RGB array treats the decoded samples as JFIF -- BT.601, full range -- whatever
+ * the stream says.  h2j_out_opts8 is h2j_out_opts7 with its last reserved word named.
+ * colour: 0: off, as every other call.
+ *   H2J_COLOUR_AUTO: the source's matrix and range are the stream's: the VUI video_signal_type of the H.264 / H.265
+ *     SPS (video_full_range_flag; matrix_coefficients where colour_description_present_flag is set), or, in a HEIF
+ *     file, the `nclx` colr property of the primary item, which wins over the VUI (a grid: the grid item's, else its
+ *     tiles'; rICC / prof profiles are ignored).  matrix_coefficients 1 is BT.709; 5 and 6 are BT.601; 9 is BT.2020
+ *     non-constant luminance; 2 (unspecified) or no signalling is BT.601 -- how the library reads such streams
+ *     without the option, and swscale's default.  No range signalled is limited range (E.2.1 of both specs infers
+ *     video_full_range_flag 0).  Any other matrix_coefficients (0 identity / GBR, 4, 7, 8 YCgCo, 10 constant
+ *     luminance, 11 and above, reserved values) fails that rendition alone with H2J_ERR_OUT_OPTS, the value in its
+ *     message: never a wrong picture.
+ *   H2J_COLOUR_EXPLICIT | mc << 1 | full: the caller names the source, whatever the stream says: mc in {1, 5, 6, 9} as
+ *     above, full 1 for full range, 0 for limited.
+ * The rule.  (Kr, Kb) of the source matrix: BT.601 (0.299, 0.114), BT.709 (0.2126, 0.0722), BT.2020 (0.2627, 0.0593);
+ * Kg = 1 - Kr - Kb; the target is Kr' = 0.299, Kb' = 0.114, Kg' = 0.587.  (oy, sy, sc) of the source range: limited
+ * (16, 219, 224), full (0, 255, 255).  In exact rationals, rnd rounding to nearest with halves away from zero:
+ *     a = 2 Kb'(1-Kb) - 2 Kg' Kb (1-Kb)/Kg        b = 2 Kr'(1-Kr) - 2 Kg' Kr (1-Kr)/Kg
+ *     c = (2(1-Kb) - a) / (2(1-Kb'))              d = -b / (2(1-Kb'))
+ *     e = -a / (2(1-Kr'))                         f = (2(1-Kr) - b) / (2(1-Kr'))
+ *     g = 255 / sc
+ *     LY = rnd(255/sy 2^20)   LB = rnd(a g 2^16)   LR = rnd(b g 2^16)
+ *     CB = rnd(c g 2^16)      CR = rnd(d g 2^16)   RB = rnd(e g 2^16)   RR = rnd(f g 2^16)
+ * (h2j_colour_coeffs of include/h2j_ext.h returns them).  The source is the rendition's 8-bit planes after orientation,
+ * window and scale / fit -- the planes the unsharp mask would read; a source above 8 bits through K4's conversion
+ * first.  With Cb16, Cr16 the 9-3-3-1 chroma of "RGB output" at luma position (x, y), 16 x precision, all shifts
+ * arithmetic:
+ *     Y'(x, y)  = clip((LY (Y - oy) + LB (Cb16 - 2048) + LR (Cr16 - 2048) + 2^19) >> 20, 0, 255)
+ *     Cb'(i, j) = clip((CB (Cb - 128) + CR (Cr - 128) + (128 << 16) + 2^15) >> 16, 0, 255)
+ *     Cr'(i, j) = clip((RB (Cb - 128) + RR (Cr - 128) + (128 << 16) + 2^15) >> 16, 0, 255)
+ * BT.601 full range is exactly the identity: a rendition that resolves to it is the rendition without colour.
+ * The normalised planes are the picture: the rendition's bytes are exactly those the same call without colour returns
+ * for a picture whose 8-bit planes are the normalised planes -- the unsharp mask, the pad border (its colour is sRGB
+ * and is not converted), rate control, qscale and format all act on them.
+ * Not built: transfer functions and gamut (PQ / HLG tone mapping, BT.2020 -> sRGB primaries), ICC profiles, chroma
+ * siting other than JFIF's centre, conversion at the source bit depth, colour tags in the JPEG.
+ * Any other value of colour fails that rendition alone with H2J_ERR_OUT_OPTS.  On a kernel library without the stage
+ * (h2j_gpu_colour) a converted rendition fails alone with H2J_ERR_NO_STAGE.
+ * The functions that take h2j_out_opts8 are declared in include/h2j_ext.h and exported by libH265ToJpegExt.so. */
+#define H2J_COLOUR_AUTO (-1)
+#define H2J_COLOUR_EXPLICIT 0x100
+typedef struct {
+    int32_t scale_log2, max_dim, fit_w, fit_h, flags; /* as h2j_out_opts6 */
+    int32_t crop_x, crop_y, crop_w, crop_h;           /* window of the oriented picture */
+    int32_t orient;                                   /* 0..8, or H2J_ORIENT_AUTO */
+    int32_t qscale;                                   /* 0, or 2..31 (0 with a raw format) */
+    int32_t sharpen;                                  /* 0..64, in 1/16 */
+    int32_t format;                                   /* H2J_FMT_* */
+    int32_t pad;                                      /* 0, or 1: letterbox to the box */
+    int32_t background;                               /* 0x00RRGGBB (0 without pad) */
+    int32_t colour;                                   /* 0, H2J_COLOUR_AUTO, or H2J_COLOUR_EXPLICIT | mc << 1 | full */
+} h2j_out_opts8;                                      /* 64 bytes */
+
 /* Test / inspection entry points (one picture).
  * stage: 0 final decoded picture, 1 pre-loop-filter, 2 deblocked (pre-SAO).
  * planes_out: uint16 Y (w*h) then U, V ((w/2)*(h/2)) of the cropped picture.
@@ -430,7 +484,9 @@ int h2j_engine_decode_multi5(h2j_engine *e, const uint8_t *data, size_t size, in
  * of the batch ([9] frames stays the decoded pictures)  [24] parsed: pictures whose entropy decode ran
  * [25] raw bytes: the bytes of the raw (RGB) renditions delivered ([22] includes K3c, the RGB stage)
  * [26] pad bytes: the canvas bytes K3b wrote for the padded renditions -- per canvas its three 8-bit planes, rows of
- * whole 16-byte groups ([22] includes K3b, the padding stage). */
+ * whole 16-byte groups ([22] includes K3b, the padding stage)
+ * [27] colour bytes: the plane bytes K3v wrote for the colour-converted renditions, counted the same way ([22] includes
+ * K3v, the colour stage). */
 int h2j_engine_stats(h2j_engine *e, double *out, int n);
 /* Per chunk (one GPU launch of each stage) of the last h2j_engine_transcode, in order:
  * out[3i] pictures, out[3i+1] K1 ms, out[3i+2] K0..K5 ms (HIP events on the chunk's stream).

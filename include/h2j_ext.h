@@ -4,7 +4,8 @@
  * include/h2j.h declares what libH265ToJpeg.so exports, and that list of names does not change.  Entry points added
  * since are exported by libH265ToJpegExt.so, a thin library built beside it that forwards to it: link
  * -lH265ToJpegExt -lH265ToJpeg, or open both from an FFI binding (h2j.py does).  The types and constants they use are
- * in include/h2j.h.  So far: padded output (h2j.h "Padded output", h2j_out_opts7; DESIGN.md "Padded output (K3b)").
+ * in include/h2j.h.  So far: padded output (h2j.h "Padded output", h2j_out_opts7; DESIGN.md "Padded output (K3b)") and
+ * colour (h2j.h "Colour", h2j_out_opts8; DESIGN.md "Colour (K3v)").
  */
 #ifndef H2J_EXT_H
 #define H2J_EXT_H
@@ -45,6 +46,32 @@ int h2j_engine_decode_multi7(h2j_engine *e, const uint8_t *data, size_t size, in
 /* h2j_h265_to_jpeg_mem_multi6 with h2j_out_opts7 (padded output): out_wh holds the canvas of a padded rendition */
 int h2j_h265_to_jpeg_mem_multi7(const uint8_t *data, size_t size, int nrend, const h2j_out_opts7 *opts, uint8_t **jpeg,
                                 size_t *jpeg_len, int *status, int32_t *out_wh);
+
+/* Colour (h2j.h "Colour").  The multi7 calls with h2j_out_opts8; an h2j_out_opts7 item is the h2j_out_opts8 item with
+ * colour 0 (the multi7 calls keep rejecting a non-zero reserved word).  Renditions of one (orientation, window, output)
+ * and one resolved (matrix, range) share one conversion, a JPEG and a raw one alike; a converted rendition reads the
+ * scale stage's planes of an unconverted rendition of the same geometry. */
+int h2j_engine_transcode_multi8(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                const int32_t *nrend, const h2j_out_opts8 *opts, uint8_t *out, size_t out_cap,
+                                size_t *out_off, size_t *out_len, int *status, int32_t *out_wh);
+int64_t h2j_engine_submit_multi8(h2j_engine *e, int n, const uint8_t *const *data, const size_t *sizes,
+                                 const int32_t *nrend, const h2j_out_opts8 *opts, uint8_t *out, size_t out_cap,
+                                 size_t *out_off, size_t *out_len, int *status, int32_t *out_wh);
+/* h2j_engine_decode_multi7 with h2j_out_opts8; info has 21 entries: [0..17] as there, [18] the resolved source matrix
+ * (matrix_coefficients: 1, 6 or 9; 0 with colour off), [19] the resolved range (1 full, 0 limited), [20] = 1 if the
+ * rendition was converted (0: colour off, or BT.601 full range -- nothing to convert).  The planes are what K4 reads. */
+int h2j_engine_decode_multi8(h2j_engine *e, const uint8_t *data, size_t size, int nrend, const h2j_out_opts8 *opts,
+                             int pick, uint8_t *planes_out, size_t cap, int *info);
+int h2j_h265_to_jpeg_mem_multi8(const uint8_t *data, size_t size, int nrend, const h2j_out_opts8 *opts, uint8_t **jpeg,
+                                size_t *jpeg_len, int *status, int32_t *out_wh);
+/* What a stream signals, without decoding it (pure: no engine): info[0..3] = colour_primaries, transfer_characteristics,
+ * matrix_coefficients, full range (1 / 0), from the first SPS's VUI of an Annex-B stream or, in a HEIF file, the nclx
+ * colr property (which wins over the VUI); 2 / 2 / 2 / 0 where nothing is signalled.  Returns 0, or a negative status:
+ * -1 for a null argument, -100 for bytes that are no stream, the demuxer's for a HEIF file it refuses. */
+int h2j_stream_colour(const uint8_t *data, size_t size, int32_t info[4]);
+/* The constants of a source matrix (matrix_coefficients 1, 5, 6 or 9) and range (full 1 / 0): k[0..7] = oy, LY, LB, LR,
+ * CB, CR, RB, RR of h2j.h "Colour", computed with integers.  Returns 0, or H2J_ERR_OUT_OPTS (nothing is written). */
+int h2j_colour_coeffs(int matrix, int full, int32_t k[8]);
 
 #ifdef __cplusplus
 }

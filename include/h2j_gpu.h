@@ -113,6 +113,13 @@ constexpr int h2j_k3c_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) 
 #define H2J_K3B_ROWS 4
 constexpr int h2j_k3b_plane_tiles(int w, int h) { return (((h2j_spic_stride(w) >> 2) + 63) >> 6) * ((h + 4 * H2J_K3B_ROWS - 1) / (4 * H2J_K3B_ROWS)); }
 constexpr int h2j_k3b_tiles(int bw, int bh) { return h2j_k3b_plane_tiles(bw, bh) + 2 * h2j_k3b_plane_tiles(bw / 2, bh / 2); }
+/* K3v (colour) workgroups (256 lanes) of one w x h output.  The matrix class: 64 lanes of 8 adjacent luma samples x 4
+ * lane rows; lane row j makes the luma rows 2 j - 1 and 2 j from the chroma rows j - 1 and j, and converts chroma row
+ * j: h / 2 + 1 lane rows.  The range-only class: per plane, 64 dwords of 4 samples x 4 lane rows of H2J_K3V_ROWS rows */
+#define H2J_K3V_ROWS 4
+constexpr int h2j_k3v_matrix_tiles(int w, int h) { return ((((w + 7) >> 3) + 63) >> 6) * (((h >> 1) + 1 + 3) >> 2); }
+constexpr int h2j_k3v_plane_tiles(int w, int h) { return ((((w + 3) >> 2) + 63) >> 6) * ((h + 4 * H2J_K3V_ROWS - 1) / (4 * H2J_K3V_ROWS)); }
+constexpr int h2j_k3v_range_tiles(int w, int h) { return h2j_k3v_plane_tiles(w, h) + 2 * h2j_k3v_plane_tiles(w / 2, h / 2); }
 /* K3p's grid is K3s's over the coarsest level of the picture's pyramid (h2j_k3s_tiles of that level's
  * size): a lane makes 4 adjacent outputs of that level and the finer levels' outputs under them */
 #endif
@@ -262,6 +269,17 @@ int h2j_gpu_rgb(const h2j_gpu_batch *b, const h2j_rgb *map, const int32_t *first
 #define H2J_PAD_CLASSES 3
 int h2j_gpu_pad(const h2j_gpu_batch *b, const h2j_pad *map, const int32_t *first, const int32_t *count,
                 const int32_t *tiles, void *stream);
+/* K3v: the colour-converted outputs (h2j_colour, a device array), grouped by class = 2 x source class (as K3u's: 0: the
+ * 8-bit planes K3s / K3r / K3p wrote, h2j_colour.wide; 1: another 8-bit source; 2: a 16-bit source) + h2j_colour.matrix:
+ * the source planes -> planes in JFIF's matrix and range at h2j_colour.dst (DESIGN.md "Colour (K3v)").  first / count /
+ * tiles: per class (host arrays of H2J_COLOUR_CLASSES), tiles the most workgroups one output of the class needs
+ * (h2j_k3v_range_tiles, h2j_k3v_matrix_tiles); one launch per class present.  Runs after h2j_gpu_scale, whose outputs
+ * it may read, and before h2j_gpu_finish, h2j_gpu_pad, h2j_gpu_rgb and K4, which may read its; out of place.  A kernel
+ * library older than the stage lacks the symbol: the host library resolves it when it loads and fails colour-converted
+ * renditions alone (H2J_ERR_NO_STAGE) */
+#define H2J_COLOUR_CLASSES 6
+int h2j_gpu_colour(const h2j_gpu_batch *b, const h2j_colour *map, const int32_t *first, const int32_t *count,
+                   const int32_t *tiles, void *stream);
 /* K4: JPEG forward path on the frames' JPEG source views (frame.pic2, or h2j_scaled.spic of a scaled
  * picture) -> frame.jcoef / frame.jstat
  * (variance, rate control, FDCT + quantiser + zigzag, symbol histograms) */

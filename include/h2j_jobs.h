@@ -232,6 +232,30 @@ typedef struct {
     int32_t dst_off[3];             /* byte offset of each plane inside dst */
 } h2j_pad;
 
+/* One colour-converted output of a batch (DESIGN.md "Colour (K3v)"): K3v reads the planes the output's view would
+ * otherwise be before finishing -- the 8-bit planes K3s / K3r / K3p wrote (16-byte row groups), or an unscaled frame,
+ * window or oriented source in the frame's sample type -- and writes 8-bit planes of its own at dst: the source's
+ * matrix and range normalised to JFIF's (BT.601, full range) with the eight constants k (include/h2j.h "Colour").
+ * h2j_finish with the constants in the place of sharpen: the record describes its source itself (no h2j_frame is
+ * read); K3u, K3b, K3c and K4 / K5 read dst through the output's view (pic == pic2 == dst). */
+typedef struct {
+    int32_t w, h;                   /* luma size of the output (both even) */
+    int32_t k[8];                   /* oy, LY, LB, LR, CB, CR, RB, RR (h2j_colour_coeffs) */
+    int32_t matrix;                 /* 0: LB = LR = CR = RB = 0, the luma never reads chroma (range only); 1: the rest */
+    int32_t bit_depth, bit_depth_c; /* of the source samples (8: uint8_t planes, above: uint16_t) */
+    int32_t crop_x, crop_y;         /* the source's first luma sample inside its planes */
+    int32_t wide;                   /* 1: an 8-bit source with 16-byte row groups and no crop (the planes K3s / K3r /
+                                       K3p wrote): aligned dword loads */
+    uint64_t src;                   /* source planes (arena offset, bytes) */
+    int32_t src_stride[3];          /* elements per row */
+    int32_t src_off[3];             /* element offset of each plane inside src */
+    uint64_t dst;                   /* converted planes (arena offset, bytes; 256-byte aligned) */
+    int32_t dst_stride[3];          /* bytes per row (h2j_spic_stride: multiples of 16) */
+    int32_t dst_off[3];             /* byte offset of each plane inside dst */
+    uint64_t jstat;                 /* the h2j_jstat of this output: K3v clears its var_sum, K4a sums the converted
+                                       picture's */
+} h2j_colour;
+
 /* h2j_frame.strong_smoothing bit 1: RExt intra_smoothing_disabled_flag (no reference filtering) */
 #define H2J_NO_INTRA_SMOOTHING 2
 /* h2j_frame.rext: implicit RDPCM of transform-skip / bypass TBs predicted with mode 10 / 26;

@@ -187,6 +187,7 @@ typedef struct {
 
 typedef struct {
     int W, H, outW, outH, mbw, mbh, bd, qp, t8x8, pcm, qpdelta, slice_rows, alpha, beta, dbidc, cqp, cqp2, cavlc, sm, nonidr, delay, firstmb, vuireorder, vuicpb, ilsps, lossless, mbaff, cur_field, paff, onefield, mono;
+    int colour, col[4]; /* --colour P,T,M,F: video_signal_type in the VUI (M < 0: no colour description) */
     long long rawcrop[4];
     uint16_t *src[3], *rec[3];
     int st[3];
@@ -1181,9 +1182,16 @@ static void write_sps(FILE *f, G *g, int profile) {
     /* --vuireorder K: the VUI's reorder depth alone (no extra pictures; malformed-SPS vectors use
      * K > 16); --vuicpb K: a NAL HRD with cpb_cnt_minus1 = K (K > 31 is malformed) */
     const int reorder = g->vuireorder >= 0 ? g->vuireorder : g->delay;
-    const int vui = g->delay > 0 || g->vuireorder >= 0 || g->vuicpb >= 0;
+    const int vui = g->delay > 0 || g->vuireorder >= 0 || g->vuicpb >= 0 || g->colour;
     bw_put(&b, (uint32_t)vui, 1); /* vui_parameters_present_flag */
     if (vui) { /* E.1.1: bitstream_restriction carrying the reorder depth (+ an optional NAL HRD) */
+        if (g->colour) {
+            bw_put(&b, 0, 2);   /* aspect, overscan */
+            bw_put(&b, 1, 1); bw_put(&b, 5, 3); bw_put(&b, (uint32_t)(g->col[3] != 0), 1); /* video signal, range */
+            bw_put(&b, g->col[2] >= 0, 1);                                                  /* colour_description_present_flag */
+            if (g->col[2] >= 0) { bw_put(&b, (uint32_t)g->col[0], 8); bw_put(&b, (uint32_t)g->col[1], 8); bw_put(&b, (uint32_t)g->col[2], 8); }
+            bw_put(&b, 0, 2);   /* chroma loc, timing */
+        } else
         bw_put(&b, 0, 5);       /* aspect, overscan, video signal, chroma loc, timing */
         bw_put(&b, g->vuicpb >= 0, 1); /* nal_hrd_parameters_present_flag */
         if (g->vuicpb >= 0) {   /* E.1.2 */
@@ -1260,6 +1268,10 @@ int main(int argc, char **argv) {
     g->firstmb = opt_int(argc, argv, "--firstmb", -1);
     g->vuireorder = opt_int(argc, argv, "--vuireorder", -1);
     g->vuicpb = opt_int(argc, argv, "--vuicpb", -1);
+    if (opt_str(argc, argv, "--colour")) { /* --colour P,T,M,F: video_signal_type (M = -1: no colour description) */
+        g->colour = 1;
+        sscanf(opt_str(argc, argv, "--colour"), "%d,%d,%d,%d", &g->col[0], &g->col[1], &g->col[2], &g->col[3]);
+    }
     g->ilsps = opt_int(argc, argv, "--ilsps", 0);
     /* --mbaff 1: an MBAFF frame (frame_mbs_only_flag 0, mb_adaptive_frame_field_flag 1): macroblock
      * pairs, each coded as two frame or two field macroblocks (random per pair, --fieldpct % field) */

@@ -22,7 +22,9 @@
  *            --beta B --tc T --recon out.yuv --cbqp N --crqp N
  *            --sl 0..4 (scaling lists, see write_scaling_list_data)
  *   range extensions (H.265 v2): --profile P (general_profile_idc; default 1 / 2 / 4 for
- *            8 / 10 / other bit depths), --vui 1 (a VUI with HRD parameters),
+ *            8 / 10 / other bit depths), --vui 1 (a VUI with HRD parameters), --colour P,T,M,F (a VUI of
+ *            video_signal_type alone: colour_primaries, transfer_characteristics, matrix_coefficients and the
+ *            full-range flag; M = -1: no colour description),
  *            --rext MASK (sps_range_extension flags: 1 transform_skip_rotation, 2
  *            transform_skip_context, 4 implicit_rdpcm, 8 explicit_rdpcm, 16
  *            extended_precision_processing, 32 intra_smoothing_disabled, 64
@@ -234,6 +236,7 @@ typedef struct {
     long long rawconf[4]; /* --conf: raw conformance window offsets (-1: derived from the size) */
     int wdelta;           /* --wdelta: subtracted from the signalled picture width */
     int profile, vui, rext, maxts, sao_scale[2], cqo, ppsext;
+    int colour, col[4]; /* --colour P,T,M,F: a VUI of video_signal_type alone (M < 0: no colour description) */
     int cqo_len, cqo_depth, cqo_cb[6], cqo_cr[6]; /* chroma QP offset list (--cqolist, --cqodepth) */
     int eff_maxts;        /* log2 max transform-skip size the decoder uses (2 without the PPS range ext) */
 } Opt;
@@ -1352,7 +1355,16 @@ static void write_sps(FILE *f, const Opt *o) {
     bw_put(&b, 0, 1);      /* long term */
     bw_put(&b, 0, 1);      /* temporal mvp */
     bw_put(&b, (uint32_t)o->strong, 1);
-    bw_put(&b, (uint32_t)o->vui, 1); /* vui_parameters_present_flag */
+    bw_put(&b, (uint32_t)(o->vui || o->colour), 1); /* vui_parameters_present_flag */
+    if (o->colour && !o->vui) { /* E.2.1 with video_signal_type alone */
+        bw_put(&b, 0, 2);                                                           /* aspect, overscan */
+        bw_put(&b, 1, 1); bw_put(&b, 5, 3); bw_put(&b, (uint32_t)(o->col[3] != 0), 1); /* video signal, range */
+        bw_put(&b, o->col[2] >= 0, 1);                                              /* colour_description_present_flag */
+        if (o->col[2] >= 0) { bw_put(&b, (uint32_t)o->col[0], 8); bw_put(&b, (uint32_t)o->col[1], 8); bw_put(&b, (uint32_t)o->col[2], 8); }
+        bw_put(&b, 0, 1);                                                           /* chroma loc */
+        bw_put(&b, 0, 3);
+        bw_put(&b, 0, 3);                                                           /* display window, timing, bitstream restriction */
+    }
     if (o->vui) { /* E.2.1 with every optional part present, HRD (E.2.2) with NAL + VCL parameters */
         bw_put(&b, 1, 1); bw_put(&b, 255, 8); bw_put(&b, 4, 16); bw_put(&b, 3, 16); /* EXTENDED_SAR 4:3 */
         bw_put(&b, 1, 1); bw_put(&b, 0, 1);                                         /* overscan */
@@ -1558,6 +1570,10 @@ int main(int argc, char **argv) {
         sscanf(opt_str(argc, argv, "--conf"), "%lld,%lld,%lld,%lld", &o->rawconf[0], &o->rawconf[1], &o->rawconf[2], &o->rawconf[3]);
     o->profile = opt_int(argc, argv, "--profile", o->bd == 8 ? 1 : (o->bd == 10 ? 2 : 4));
     o->vui = opt_int(argc, argv, "--vui", 0);
+    if (opt_str(argc, argv, "--colour")) {
+        o->colour = 1;
+        sscanf(opt_str(argc, argv, "--colour"), "%d,%d,%d,%d", &o->col[0], &o->col[1], &o->col[2], &o->col[3]);
+    }
     o->rext = opt_int(argc, argv, "--rext", 0);
     o->maxts = opt_int(argc, argv, "--maxts", 2);
     o->cqo = opt_int(argc, argv, "--cqo", 0);

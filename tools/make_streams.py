@@ -19,6 +19,7 @@ reconstruction bit-for-bit.
   python tools/make_streams.py malformed -> tests/golden/malformed/ (out-of-range SPS / slice header values)
   python tools/make_streams.py heavy     -> tests/golden/bench_heavy/hevc1080h_XX.h265 (16 streams, ~100-250 KB)
   python tools/make_streams.py heif      -> tests/golden/heif/ (tile pictures of HEIF grids, sets a-e, and H.264 tiles)
+  python tools/make_streams.py colour    -> tests/golden/colour/ (VUI video_signal_type: matrix and range signalled, or not)
   python tools/make_streams.py aim       -> tests/golden/bench_aim/hevc1080a_XX.h265 (64 streams, QP 22-37, 110-220 KB)
 """
 import glob
@@ -695,9 +696,41 @@ def heif():
     json.dump(manifest, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1)
 
 
+# (file, codec, W, H, bit depth, qp, --colour P,T,M,F or None: no VUI): what colour="auto" has to read
+COLOUR_SETS = [
+    ("c709_limited.hevc", 265, 96, 64, 8, 30, (1, 1, 1, 0)),
+    ("c2020_limited_10b.hevc", 265, 64, 48, 10, 30, (9, 16, 9, 0)),
+    ("c709_full.avc", 264, 64, 64, 8, 28, (1, 1, 1, 1)),
+    ("cnodesc_full.hevc", 265, 48, 32, 8, 32, (2, 2, -1, 1)),  # a full-range flag and no colour description
+    ("cnovui.avc", 264, 48, 48, 8, 30, None),
+    ("cmc8_ycgco.hevc", 265, 32, 32, 8, 32, (1, 1, 8, 0)),    # a matrix the library does not convert
+]
+
+
+def colour():
+    """tests/golden/colour/: small pictures whose SPS signals a colour matrix and range, or does not (named .hevc /
+    .avc: the stream suites do not walk them).  manifest.json states what each signals -- primaries, transfer, matrix,
+    full range; 2 / 2 / 2 / 0 where absent -- so the tests never ask the parser under test."""
+    out_dir = os.path.join(ROOT, "tests/golden/colour")
+    os.makedirs(out_dir, exist_ok=True)
+    planes = source_planes()
+    manifest = []
+    for i, (name, codec, w, h, bd, qp, col) in enumerate(COLOUR_SETS):
+        content = make_content(planes, w, h, 900 + i, 3, bd)
+        path = os.path.join(out_dir, name)
+        opts = [] if col is None else ["--colour", ",".join(str(x) for x in col)]
+        nb = encode(content, w, h, bd, qp, 9000 + i, path, opts, codec=codec)
+        sig = (2, 2, 2, 0) if col is None else ((col[0], col[1], col[2]) if col[2] >= 0 else (2, 2, 2)) + (col[3],)
+        manifest.append({"file": name, "codec": codec, "w": w, "h": h, "bit_depth": bd, "qp": qp, "vui": col is not None,
+                         "primaries": sig[0], "transfer": sig[1], "matrix": sig[2], "full_range": sig[3]})
+        print(f"{path}: {nb} B", flush=True)
+    json.dump(manifest, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1)
+
+
 if __name__ == "__main__":
     build_gen()
     what = sys.argv[1] if len(sys.argv) > 1 else "bench"
     {"bench": bench, "parity": parity, "4k": fourk, "parity264": parity264, "bench264": bench264,
      "mixed": mixed, "f3": f3, "heavy": heavy, "malformed": malformed, "nosdh": nosdh, "entropy": entropy,
-     "wide264": wide264, "leftcrop": leftcrop, "heavy264": heavy264, "tall264": tall264, "aim": aim, "heif": heif}[what]()
+     "wide264": wide264, "leftcrop": leftcrop, "heavy264": heavy264, "tall264": tall264, "aim": aim, "heif": heif,
+     "colour": colour}[what]()
