@@ -639,13 +639,14 @@ DEVI void hevc_residual_group(const K0F& f, const uint4& rec, uint64_t gm, int G
     // into rows 0 mod 4 (EE) and 2 mod 4 (EO).  Slots past jmax hold zeros, so a slot whose first
     // input is <= jmax is taken whole.
     constexpr int L = LOG2N - 2;
-    auto pass = [&](int jmax, auto inpair, int (&acc)[N]) __attribute__((always_inline)) {
+    // `rnd`, the rounding term of the shift that follows the pass, starts the sums (EE reaches every output with +).
+    auto pass = [&](int jmax, int rnd, auto inpair, int (&acc)[N]) __attribute__((always_inline)) {
         if constexpr (N >= 8) {
             int E[N / 2], O[N / 2], EE[N / 4], EO[N / 4];
 #pragma unroll
             for (int i = 0; i < N / 2; i++) O[i] = 0;
 #pragma unroll
-            for (int i = 0; i < N / 4; i++) EE[i] = EO[i] = 0;
+            for (int i = 0; i < N / 4; i++) EE[i] = rnd, EO[i] = 0;
             for (int ps = 0; ps < N / 8 && 8 * ps <= jmax; ps++) {
                 const int v = inpair(ps);
 #pragma unroll
@@ -673,7 +674,7 @@ DEVI void hevc_residual_group(const K0F& f, const uint4& rec, uint64_t gm, int G
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < N; i++) acc[i] = 0;
+            for (int i = 0; i < N; i++) acc[i] = rnd;
             for (int ps = 0; ps < 2 && 2 * ps <= jmax; ps++) {
                 const int v = inpair(ps);
 #pragma unroll
@@ -686,25 +687,26 @@ DEVI void hevc_residual_group(const K0F& f, const uint4& rec, uint64_t gm, int G
     const int qcol = 2 * k0_pslot<N>(q) + k0_phalf<N>(q);  // this lane's column in the paired tmp rows
     {  // columns: tmp[y][x] = clip16((sum_j M[j][y] * d[j][x] + 64) >> 7)
         int acc[N];
-        if (act) pass(myy, [&](int ps) { return blk32[g * (NN / 2) + ps * N + q]; }, acc);
+        if (act) pass(myy, 64, [&](int ps) { return blk32[g * (NN / 2) + ps * N + q]; }, acc);
         wave_sync();  // tmp overlays blk (K0LdsHevc): every column has been read
         if (act) {
 #pragma unroll
-            for (int i = 0; i < N; i++) tmp[g * NP + i * P + qcol] = static_cast<int16_t>(clip3(-32768, 32767, (acc[i] + 64) >> 7));
+            for (int i = 0; i < N; i++) tmp[g * NP + i * P + qcol] = static_cast<int16_t>(clip3(-32768, 32767, acc[i] >> 7));
         }
     }
     wave_sync();
-    if (act) {  // rows: r[y][x] = (sum_j M[j][x] * tmp[y][j] + rnd) >> (20 - bitDepth)
+    if (act) {  // rows: r[y][x] = clip16((sum_j M[j][x] * tmp[y][j] + rnd) >> (20 - bitDepth))
         int acc[N];
-        pass(mxx, [&](int ps) { return tmp32[(g * NP + q * P) / 2 + ps]; }, acc);
         const int bdS = 20 - (mine.c ? f.bdc : f.bd);
+        pass(mxx, 1 << (bdS - 1), [&](int ps) { return tmp32[(g * NP + q * P) / 2 + ps]; }, acc);
         const int c = mine.c;
         int16_t* R = hevc_res_at(res, f.width, f.height, f.log2ctb, c, mine.x, mine.y) + (q << h2j_res_q(f.log2ctb, c));
         uint32_t packed[N / 2];
 #pragma unroll
         for (int i = 0; i < N / 2; i++) {
-            const int a = (acc[2 * i] + (1 << (bdS - 1))) >> bdS, b = (acc[2 * i + 1] + (1 << (bdS - 1))) >> bdS;
-            packed[i] = (static_cast<uint32_t>(a) & 0xFFFF) | (static_cast<uint32_t>(b) << 16);
+            const int a = acc[2 * i] >> bdS, b = acc[2 * i + 1] >> bdS;
+            // clip16 as after the column pass: v_cvt_pk_i16_i32 saturates both halves
+            packed[i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(a, b));
         }
         if (N == 4) {
             *reinterpret_cast<uint2*>(R) = make_uint2(packed[0], packed[1]);

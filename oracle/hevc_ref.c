@@ -680,7 +680,8 @@ static void inv_transform(const int *d, int *r, int n, int dst, int bd) {
     int bdShift = 20 - bd;
     for (int y = 0; y < n; y++) {
         inv_1d(tmp + y * n, out, n, dst);
-        for (int x = 0; x < n; x++) r[y * n + x] = (out[x] + (1 << (bdShift - 1))) >> bdShift;
+        /* clipped to int16 after both passes, as FFmpeg's hevcdsp template (SCALE); DESIGN.md §5 */
+        for (int x = 0; x < n; x++) r[y * n + x] = clip3(-32768, 32767, (out[x] + (1 << (bdShift - 1))) >> bdShift);
     }
 }
 

@@ -100,6 +100,10 @@ HEVC_CASES = [
                                                  "--cqodepth", "0", "--ctb", "32"]),
     ("cqo_len6_depth3_bypass", 128, 96, 8, 26, ["--profile", "4", "--cqo", "2", "--cqolist",
                                                  "-12,12,5,-5,0,0,3,7,-6,-2,10,-9", "--cqodepth", "3", "--bypass", "1"]),
+    # designed levels up to 32767 / -32768 (--inject, tests/golden/k0levels): tier 1 in range, tier 2 past the
+    # dequantisation clip, the clip between the transform stages and, at 12 bits, the one after the second stage
+    ("inject_tier1_10bit", 128, 96, 10, 8, ["--inject", "1,1,2", "--ctb", "32"]),
+    ("inject_tier2_12bit_sl", 128, 128, 12, 2, ["--inject", "2,2,3", "--ctb", "32", "--sl", "2", "--depth", "0"]),
 ]
 
 

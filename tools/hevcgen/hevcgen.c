@@ -21,6 +21,8 @@
  *            --depth D (max_transform_hierarchy_depth_intra) --ctb 16|32|64
  *            --beta B --tc T --recon out.yuv --cbqp N --crqp N
  *            --sl 0..4 (scaling lists, see write_scaling_list_data)
+ *            --inject T[,num,den] (designed large-level patterns in num TBs of den, default 1 of 2;
+ *            T = 1 in range, 2 past the decoder's clips: see inject_levels)
  *   range extensions (H.265 v2): --profile P (general_profile_idc; default 1 / 2 / 4 for
  *            8 / 10 / other bit depths), --vui 1 (a VUI with HRD parameters), --colour P,T,M,F (a VUI of
  *            video_signal_type alone: colour_primaries, transfer_characteristics, matrix_coefficients and the
@@ -239,6 +241,7 @@ typedef struct {
     int colour, col[4]; /* --colour P,T,M,F: a VUI of video_signal_type alone (M < 0: no colour description) */
     int cqo_len, cqo_depth, cqo_cb[6], cqo_cr[6]; /* chroma QP offset list (--cqolist, --cqodepth) */
     int eff_maxts;        /* log2 max transform-skip size the decoder uses (2 without the PPS range ext) */
+    int inject, inject_num, inject_den; /* --inject T[,num,den]: designed level patterns in num TBs of den (inject_levels) */
 } Opt;
 #define RX_ROT 1
 #define RX_CTX 2
@@ -343,7 +346,7 @@ static void inv_transform(const int *d, int *r, int n, int dst, int bd) {
         for (int x = 0; x < n; x++) {
             long s = 0;
             for (int j = 0; j < n; j++) s += (long)coefm(dst, n, j, x) * tmp[y * n + j];
-            r[y * n + x] = (int)((s + (1L << (bdShift - 1))) >> bdShift);
+            r[y * n + x] = clip3(-32768, 32767, (int)((s + (1L << (bdShift - 1))) >> bdShift)); /* as the decoder */
         }
 }
 
@@ -667,6 +670,7 @@ static void enc_residual(G *g, int *coef, int log2n, int c, int pred_mode, int t
  * the subblock's absolute sum (decoder rule in residual_coding) by growing
  * the highest-frequency coefficient of the subblock by one.  Applied before
  * reconstruction so encoder and decoder agree. */
+static int g_injected; /* the block code_block() coded last carries an --inject pattern */
 static void sdh_fix(G *g, int *coef, int log2n, int c, int pred_mode, int tskip) {
     const int n = 1 << log2n;
     if (!g->o.sdh || g->cu_bypass) return;
@@ -691,7 +695,10 @@ static void sdh_fix(G *g, int *coef, int log2n, int c, int pred_mode, int tskip)
         int neg = coef[fy * n + fx] < 0;
         if ((sum & 1) != neg) {
             int lx = (xs << 2) + sc[2][last][0], ly = (ys << 2) + sc[2][last][1];
-            coef[ly * n + lx] += coef[ly * n + lx] > 0 ? 1 : -1;
+            /* (--inject: a designed block's level shrinks instead, so that no dequantised value
+             * leaves the pattern's bound or the int16 level range; a level of +-1 has to grow) */
+            int v = coef[ly * n + lx], grow = !(g_injected && abs(v) >= 2) && abs(v) < 32767;
+            coef[ly * n + lx] += (v > 0) == grow ? 1 : -1;
         }
     }
 }
@@ -809,6 +816,98 @@ static void diff_dpcm(int *r, int n, int vertical) {
 }
 static int uses_rdpcm(G *g, int mode) { return (g->o.rext & RX_RDPCM) && (mode == 10 || mode == 26); }
 
+/* --inject T[,num,den]: num transform blocks of den (seeded) code a designed level pattern instead of
+ * the quantised residual, cycling through the patterns per (component class, size) so that a
+ * picture with enough blocks of a size carries all of them; the encoder goes on closed-loop from
+ * the decoder-side reconstruction.  The patterns are designed on the dequantised coefficient d
+ * (8.6.3) and coded as the level that dequantises to it at the block's QP and scaling factor.
+ * With S[j][k] = sign(M[j][y0] * M[k][x0]) ("aligned": every term of output sample (x0, y0) of
+ * the inverse transform has one sign):
+ *   T = 1, large but in range (no dequantisation clip, no clip after the column pass, row-pass
+ *   result inside int16): 0-3 a single coefficient at the corners (0,0), (N-1,0), (0,N-1),
+ *   (N-1,N-1) with d = +max, -max, -max, +max; 4 a single coefficient in row 1 with d = -max;
+ *   5 a full block S * a, a the largest magnitude that keeps both passes in range; 6 a full block
+ *   of random signs and magnitudes <= a.  Transform-skip blocks take 0-3, 5, 6 with max and a cut
+ *   to what the shift by 15 - bitDepth - log2n keeps inside int16.
+ *   T = 2, past the clips: 0 / 1 a single level 32767 in row 1 / -32768 at (N-1,N-1) (dequantisation
+ *   clips where the scale exceeds 1); 2 / 3 one column of +-S at d = max (column-pass clip);
+ *   4 / 5 the full block +-S of levels 32767 / -32768, x0 the column of the largest L1 norm (every
+ *   clip, and the row-pass result past int16 where the norm allows); 6 / 7 the full block +-S at
+ *   d = max without a dequantisation clip.  Transform-skip blocks are left alone. */
+static long inj_deq(long lvl, long num, int sh) { return (lvl * num + (1L << (sh - 1))) >> sh; }
+/* the level of want's sign whose dequantised value is the largest in magnitude within |want| */
+static int inj_level(int want, int m, int qp, int sh) {
+    const long num = ((long)m * k_ls[qp % 6]) << (qp / 6);
+    const long a = labs((long)want), sg = want < 0 ? -1 : 1, lmax = want < 0 ? 32768 : 32767;
+    long l = (a << sh) / num;
+    if (l > lmax) l = lmax;
+    while (l < lmax && labs(inj_deq(sg * (l + 1), num, sh)) <= a) l++;
+    while (l > 0 && labs(inj_deq(sg * l, num, sh)) > a) l--;
+    return (int)(sg * l);
+}
+static int g_inj_count[2][4];
+static int inject_levels(G *g, int c, int log2n, int qp, int tskip, int *coef) {
+    const int n = 1 << log2n, bd = g->o.bd, dst = c == 0 && log2n == 2, sh = bd + log2n - 5, bdS = 20 - bd;
+    const int tier = g->o.inject;
+    if (tier == 2 && tskip) return -1;
+    const int k = g_inj_count[c > 0][log2n - 2]++;
+    int pat = k % (tier == 1 ? 7 : 8);
+    if (tier == 1 && tskip && pat == 4) pat = 5;
+    long l1[32], l1max = 0;
+    int xmax = 0;
+    for (int i = 0; i < n; i++) {
+        l1[i] = 0;
+        for (int j = 0; j < n; j++) l1[i] += abs(coefm(dst, n, j, i));
+        if (l1[i] > l1max) { l1max = l1[i]; xmax = i; }
+    }
+    int x0 = (5 * (k / 7) + 1) % n, y0 = (3 * (k / 7) + 2) % n;
+    int dmax = 32767, dmin = -32768;
+    long a;
+    if (tskip) { /* r = d << -(15 - bd - log2n) stays inside int16 */
+        int ts = 15 - bd - log2n;
+        if (ts < 0) { dmax >>= -ts; dmin = -(32768 >> -ts); }
+        a = dmax;
+    } else {
+        long a1 = (32767L << 7) / l1max, a2 = (32767L << (7 + bdS)) / (l1max * l1max);
+        a = (a1 < a2 ? a1 : a2) - 1; /* column pass <= 32767 and row pass <= 32767 whatever the signs */
+    }
+    memset(coef, 0, sizeof(int) * n * n);
+#define INJ_M(i) ((tskip && n > 4) ? 16 : sf(c, log2n, (i)))
+#define INJ_S(j, kk) ((tskip ? 1 : (coefm(dst, n, (j), y0) < 0 ? -1 : 1) * (coefm(dst, n, (kk), x0) < 0 ? -1 : 1)))
+    if (tier == 1) {
+        if (pat <= 4) {
+            static const int py[5] = {0, 1, 0, 1, 0}, px[5] = {0, 0, 1, 1, 0};
+            int i = pat == 4 ? n : py[pat] * (n - 1) * n + px[pat] * (n - 1);
+            coef[i] = inj_level(pat == 0 || pat == 3 ? dmax : dmin, INJ_M(i), qp, sh);
+        } else {
+            for (int j = 0; j < n; j++)
+                for (int kk = 0; kk < n; kk++) {
+                    int i = j * n + kk;
+                    long want = pat == 5 ? INJ_S(j, kk) * a : (rndn(2) ? -1 : 1) * (1 + (long)rndn((int)a));
+                    coef[i] = inj_level((int)want, INJ_M(i), qp, sh);
+                }
+        }
+    } else {
+        const int neg = pat & 1;
+        if (pat == 0) coef[n] = 32767;
+        else if (pat == 1) coef[n * n - 1] = -32768;
+        else {
+            if (pat == 4 || pat == 5) x0 = xmax;
+            for (int j = 0; j < n; j++)
+                for (int kk = 0; kk < n; kk++) {
+                    int i = j * n + kk, s = INJ_S(j, kk) * (neg ? -1 : 1);
+                    if (pat <= 3 && kk != x0) continue;
+                    coef[i] = pat == 4 || pat == 5 ? (s < 0 ? -32768 : 32767) : inj_level(s < 0 ? -32768 : 32767, INJ_M(i), qp, sh);
+                }
+        }
+    }
+#undef INJ_M
+#undef INJ_S
+    int nz = 0;
+    for (int i = 0; i < n * n; i++) nz |= coef[i] != 0;
+    return nz;
+}
+
 /* Encode-side processing of one transform block: prediction already in
  * rec; computes levels into coef, reconstructs rec.  Returns cbf. */
 static int code_block(G *g, int c, int x0, int y0, int log2n, int pred_mode, int qp, int *coef, int *tskip_out,
@@ -821,6 +920,7 @@ static int code_block(G *g, int c, int x0, int y0, int log2n, int pred_mode, int
     int tskip = 0;
     int dst = (c == 0 && log2n == 2);
     (void)maxv;
+    g_injected = 0;
     if (g->cu_bypass) {
         if (uses_rdpcm(g, pred_mode)) diff_dpcm(res, n, pred_mode == 26); /* lossless: levels = differences */
         for (int i = 0; i < n * n; i++) { coef[i] = res[i]; nz |= res[i] != 0; }
@@ -845,6 +945,10 @@ static int code_block(G *g, int c, int x0, int y0, int log2n, int pred_mode, int
             if (l > 32767) l = 32767;
             coef[i] = tc[i] < 0 ? -l : l;
             nz |= l != 0;
+        }
+        if (g->o.inject && rndn(g->o.inject_den) < g->o.inject_num) {
+            int inz = inject_levels(g, c, log2n, qp, tskip, coef);
+            if (inz >= 0) { nz = inz; g_injected = 1; }
         }
     }
     *tskip_out = tskip;
@@ -1576,6 +1680,10 @@ int main(int argc, char **argv) {
     }
     o->rext = opt_int(argc, argv, "--rext", 0);
     o->maxts = opt_int(argc, argv, "--maxts", 2);
+    o->inject_num = 1;
+    o->inject_den = 2;
+    if (opt_str(argc, argv, "--inject")) sscanf(opt_str(argc, argv, "--inject"), "%d,%d,%d", &o->inject, &o->inject_num, &o->inject_den);
+    if (o->inject < 0 || o->inject > 2 || o->inject_den < 1) { fprintf(stderr, "--inject wants T[,num,den], T = 1 or 2\n"); return 2; }
     o->cqo = opt_int(argc, argv, "--cqo", 0);
     o->cqo_depth = opt_int(argc, argv, "--cqodepth", 1);
     {

@@ -20,6 +20,7 @@ reconstruction bit-for-bit.
   python tools/make_streams.py heavy     -> tests/golden/bench_heavy/hevc1080h_XX.h265 (16 streams, ~100-250 KB)
   python tools/make_streams.py heif      -> tests/golden/heif/ (tile pictures of HEIF grids, sets a-e, and H.264 tiles)
   python tools/make_streams.py colour    -> tests/golden/colour/ (VUI video_signal_type: matrix and range signalled, or not)
+  python tools/make_streams.py k0levels  -> tests/golden/k0levels/ (designed levels up to the int16 range: K0's clips)
   python tools/make_streams.py aim       -> tests/golden/bench_aim/hevc1080a_XX.h265 (64 streams, QP 22-37, 110-220 KB)
 """
 import glob
@@ -726,6 +727,61 @@ def colour():
         print(f"{path}: {nb} B", flush=True)
     json.dump(manifest, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1)
 
+# (name, tier, bit depth, qp, seed, options): tests/golden/k0levels/.  The QPs put Qp'Y near 22 (tier 1) / 28 (tier 2)
+# at every bit depth, so that the dequantisation scale of a 32x32 block is above 1 and a level of 32767 clips
+K0LEVELS = [
+    ("a08", 1, 8, 22, 1, []),
+    ("a10", 1, 10, 10, 2, []),
+    ("a12", 1, 12, -2, 3, []),
+    ("a08_sl", 1, 8, 24, 4, ["--sl", "2"]),
+    ("a12_ts32", 1, 12, 0, 5, ["--profile", "4", "--maxts", "5"]),
+    ("b08", 2, 8, 28, 6, []),
+    ("b10", 2, 10, 16, 17, []),
+    ("b12", 2, 12, 4, 8, []),
+    ("b10_sl", 2, 10, 14, 9, ["--sl", "3"]),
+]
+
+
+def k0levels_content(bd, seed):
+    """128 x 128, sixteen 32 x 32 CTBs: piecewise-constant luma whose pieces are 32 (twelve CTBs), 16 (two), 8 and 4
+    (one each) samples wide, so that the encoder's variance rule makes coding blocks, and with them transform blocks,
+    of every size; a little noise gives the blocks that are not injected a residual of their own"""
+    rng = np.random.default_rng(seed)
+    sc = 1 << (bd - 8)
+    kinds = [32, 32, 16, 32, 32, 8, 32, 32, 32, 32, 4, 32, 16, 32, 32, 32]
+    y = np.zeros((128, 128))
+    for i, b in enumerate(kinds):
+        ty, tx = divmod(i, 4)
+        piece = 128 + rng.integers(-40, 41, (32 // b, 32 // b)) if b < 32 else np.full((1, 1), 128 + rng.integers(-8, 9))
+        y[ty * 32:ty * 32 + 32, tx * 32:tx * 32 + 32] = np.kron(piece, np.ones((b, b)))
+    y = y * sc + rng.normal(0, 0.5 * sc, y.shape)
+    c = [np.full((64, 64), 128.0 * sc) + rng.normal(0, 0.5 * sc, (64, 64)) for _ in range(2)]
+    return [np.clip(np.rint(p), 0, (1 << bd) - 1).astype(np.int32) for p in [y] + c]
+
+
+def k0levels():
+    """tests/golden/k0levels/: pictures whose transform blocks carry hevcgen's --inject patterns (levels up to 32767 and
+    -32768), tier 1 large but inside every clip of 8.6.2-8.6.4, tier 2 past them; three of four blocks are injected.
+    manifest.json keeps each vector's options and its census by tests/k0_ref.py, which tests/test_k0_levels.py
+    recomputes and holds against the conditions the vectors are there for."""
+    import tempfile
+
+    import k0_ref as K
+    out_dir = os.path.join(ROOT, "tests/golden/k0levels")
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = []
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = K.build_dumper(os.path.join(tmp, "tu_dump"))
+        for name, tier, bd, qp, seed, opts in K0LEVELS:
+            path = os.path.join(out_dir, f"{name}.h265")
+            opts = ["--ctb", "32", "--depth", "0", "--inject", f"{tier},3,4"] + opts  # (depth 0: a 32 x 32 CU is one TB)
+            nb = encode(k0levels_content(bd, 1100 + seed), 128, 128, bd, qp, 1100 + seed, path, opts)
+            K.dump(exe, [(path, os.path.join(tmp, "d.bin"))])
+            manifest.append({"file": f"{name}.h265", "tier": tier, "w": 128, "h": 128, "bit_depth": bd, "qp": qp,
+                             "seed": 1100 + seed, "options": opts, "census": K.census(os.path.join(tmp, "d.bin"))})
+            print(f"{path}: {nb} B", flush=True)
+    json.dump(manifest, open(os.path.join(out_dir, "manifest.json"), "w"), indent=1, sort_keys=True)
+
 
 if __name__ == "__main__":
     build_gen()
@@ -733,4 +789,4 @@ if __name__ == "__main__":
     {"bench": bench, "parity": parity, "4k": fourk, "parity264": parity264, "bench264": bench264,
      "mixed": mixed, "f3": f3, "heavy": heavy, "malformed": malformed, "nosdh": nosdh, "entropy": entropy,
      "wide264": wide264, "leftcrop": leftcrop, "heavy264": heavy264, "tall264": tall264, "aim": aim, "heif": heif,
-     "colour": colour}[what]()
+     "colour": colour, "k0levels": k0levels}[what]()
